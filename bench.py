@@ -20,7 +20,13 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
          --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints exactly one JSON line.
+Rank 0 prints exactly one JSON line. A plain run sets up, warms up, times
+``--steps`` steps and reports. ``--dump-outputs DIR`` additionally writes what
+the last timed step returned (inference: the last stack's five scale maps;
+training: the loss and a fixed sample of the updated weights) as float32
+``DIR/<name>.npy``; inputs and initial weights are seeded, so two builds can be
+compared output for output. ``--full`` enables the side measurements that the
+headline figure does not need.
 """
 from __future__ import annotations
 
@@ -59,7 +65,31 @@ def parse_args():
                    help="capture the inference forward in a hipGraph and replay")
     p.add_argument("--allow-eager", action="store_true",
                    help="permit eager fallback if the HIP extension is absent")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements that are not part of the "
+                        "headline figure (with IBP_DDP_TIMING=1: untimed DDP "
+                        "all-reduce exposure steps on multi-rank train runs); "
+                        "a plain run only sets up, warms up, times --steps "
+                        "steps and reports")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as float32 .npy files, at most 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = (64 * 2**20) // (4 * max(len(arrays), 1))  # elements per array
+    for name, t in arrays.items():
+        a = t.detach().to(device="cpu", dtype=torch.float32).numpy()
+        if a.size > cap:
+            # fixed seeded sample of an output too large to store whole
+            idx = np.sort(np.random.RandomState(0).choice(a.size, cap,
+                                                          replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def main():
@@ -206,12 +236,14 @@ def main():
 
             def step(i):
                 graph.replay()
-                return static_out[-1][0]
+                return static_out[-1]
         else:
             @torch.no_grad()
             def step(i):
                 out = model(img)
-                return out[-1][0]  # last stack, scale 0 (reference evaluate.py:126)
+                # last stack; its scale 0 is the map inference consumes
+                # (reference evaluate.py:126)
+                return out[-1]
 
         metric_name = "fps_512_infer"
         vs_baseline = None  # filled below from the 38.5 FPS headline
@@ -228,8 +260,9 @@ def main():
         step(i)
     sync()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(i)
+        last = step(i)
     sync()
     elapsed = time.perf_counter() - t0
 
@@ -239,8 +272,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
 
-    if os.environ.get("IBP_DDP_TIMING") == "1" and args.mode == "train" \
-            and use_cuda and distributed:
+    if args.dump_outputs and rank == 0 and last is not None:
+        if args.mode == "infer":
+            arrays = {f"last_stack_scale{s}": t for s, t in enumerate(last)}
+        else:
+            # the step's return value plus its effect: the leading elements
+            # of every updated parameter (a fixed sample of the 129M weights)
+            arrays = {"loss": last.reshape(1),
+                      "params_sample": torch.cat(
+                          [p.detach().reshape(-1)[:4096].float()
+                           for p in model.parameters()])}
+        dump_outputs(args.dump_outputs, arrays)
+
+    if args.full and os.environ.get("IBP_DDP_TIMING") == "1" \
+            and args.mode == "train" and use_cuda and distributed:
         # untimed extra steps measuring exposed vs total all-reduce time
         # (stderr only — stdout stays the single JSON contract line)
         step(0)

@@ -45,6 +45,34 @@ def test_bench_single_process_json_schema():
     assert j["value"] > 0 and j["ms_per_step"] > 0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes what the last timed step returned (the last
+    stack's five scales) as float32 .npy; --full is accepted and keeps the
+    one-line contract."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run(
+        [sys.executable, BENCH, "--steps", "2", "--warmup", "0",
+         "--nstack", "1", "--input", "128", "--batch", "1", "--full",
+         "--dump-outputs", str(out)],
+        capture_output=True, text=True, timeout=420, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _last_json_line(r.stdout)
+    assert REQUIRED_FIELDS.issubset(j.keys()), j.keys()
+    assert j["steps"] == 2
+    files = sorted(p.name for p in out.iterdir())
+    assert files == [f"last_stack_scale{s}.npy" for s in range(5)]
+    total = 0
+    for s in range(5):
+        a = np.load(out / f"last_stack_scale{s}.npy")
+        assert a.dtype == np.float32
+        # bench.py knows the 384/512/768 presets; any other --input runs 512
+        assert a.shape == (1, 50, 128 >> s, 128 >> s)
+        assert np.isfinite(a).all()
+        total += a.nbytes
+    assert total <= 64 * 2**20
+
+
 def test_bench_infer_mode_reports_vs_baseline():
     r = subprocess.run(
         [sys.executable, BENCH, "--mode", "infer", "--steps", "1",
