@@ -38,7 +38,9 @@ namespace ibp {
 
 typedef short short8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef unsigned short ushortv8 __attribute__((ext_vector_type(8)));
+typedef unsigned short ushortv4 __attribute__((ext_vector_type(4)));
 
 constexpr int BK = 64;        // K depth per step
 
@@ -60,6 +62,9 @@ struct ConvParams {
   int act;                   // leaky-relu on epilogue
   int splitk;                // K-dimension split factor (small-grid layers)
   float* ws;                 // fp32 workspace for split-K partial accumulation
+  int vec_epi;               // 1: 4-channel epilogue groups, 2: 8-channel
+  int pair_epi;              // fallback may use 2-channel (4-byte) accesses
+  int m32;                   // M (+ tile padding) fits 32-bit index math
 };
 
 // LDS tile addressing: unpadded BK-short rows with a T2 XOR swizzle — the
@@ -124,7 +129,14 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
   const long long a_m = m0 + a_row;
   int a_n = 0, a_ho = 0, a_wo = 0;
   bool a_valid_row = a_m < p.M;
-  if (a_valid_row) {
+  if (a_valid_row && p.m32) {
+    // 64-bit % and / are emulated (dozens of instructions each); these
+    // blocks live for a few microseconds, so the common case stays 32-bit
+    unsigned t = (unsigned)a_m;
+    a_wo = (int)(t % (unsigned)p.Wo); t /= (unsigned)p.Wo;
+    a_ho = (int)(t % (unsigned)p.Ho);
+    a_n = (int)(t / (unsigned)p.Ho);
+  } else if (a_valid_row) {
     long long t = a_m;
     a_wo = (int)(t % p.Wo); t /= p.Wo;
     a_ho = (int)(t % p.Ho);
@@ -304,12 +316,14 @@ a_done:
       for (int j = 0; j < BFRAG; ++j)
         bfrag[j] = *reinterpret_cast<const short8*>(
             &lds_b[buf][lds_off(col_base + j * 16 + l15, kk + kslice)]);
+      // weight fragment FIRST: D[row][col] is then (channel, pixel), which
+      // gives each lane 4 consecutive channels of one pixel (see epilogue)
       #pragma unroll
       for (int i = 0; i < AFRAG; ++i)
         #pragma unroll
         for (int j = 0; j < BFRAG; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
+              bfrag[j], afrag[i], acc[i][j], 0, 0, 0);
     }
   };
 
@@ -345,26 +359,171 @@ a_done:
     }
   }
 
-  // ---- epilogue: C/D lane map col = lane&15, row = (lane>>4)*4 + r ---------
-  const int ecol = lane & 15;
-  const int erow4 = (lane >> 4) * 4;
-  #pragma unroll
-  for (int i = 0; i < AFRAG; ++i) {
+  // ---- epilogue ------------------------------------------------------------
+  // compute() feeds the weight fragment as the first MFMA operand, so the C/D
+  // lane map (row = (lane>>4)*4 + r, col = lane&15) reads (channel, pixel):
+  // a lane's 4 accumulators are 4 CONSECUTIVE CHANNELS of one pixel. Paths,
+  // widest first (the host picks by Cout and pointer alignment):
+  //   vec_epi 2  Cout % 8 == 0, unsplit: 16-byte bf16 stores (lane exchange)
+  //   vec_epi 1+ Cout % 4 == 0: 8-byte bf16 stores / 16-byte fp32 slab stores
+  //   pair_epi   Cout % 2 == 0: 4-byte bf16 stores / 8-byte slab stores
+  //   otherwise  per element
+  // All four do the same arithmetic in the same order.
+  const int epix = lane & 15;
+  const int ech4 = (lane >> 4) * 4;
+  float* const ws_slice =
+      p.splitk > 1 ? p.ws + (long long)sk * p.M * p.Cout : nullptr;
+  // fused epilogue of one fragment: 8-byte residual loads, today's order
+  auto finish = [&](const floatx4& a, long long idx, const floatx4& sc,
+                    const floatx4& sh) -> ushortv4 {
+    ushortv4 r0 = ushortv4{0, 0, 0, 0}, r1 = r0, r2 = r0;
+    if (p.res) r0 = *reinterpret_cast<const ushortv4*>(p.res + idx);
+    if (p.res_post) r1 = *reinterpret_cast<const ushortv4*>(p.res_post + idx);
+    if (p.res_post2)
+      r2 = *reinterpret_cast<const ushortv4*>(p.res_post2 + idx);
+    ushortv4 out;
     #pragma unroll
-    for (int j = 0; j < BFRAG; ++j) {
-      int col = n0 + col_base + j * 16 + ecol;
-      if (col >= p.Cout) continue;
-      float sc = p.scale ? p.scale[col] : 1.f;
-      float sh = p.shift ? p.shift[col] : 0.f;
+    for (int r = 0; r < 4; ++r) {
+      float v = a[r] * sc[r] + sh[r];
+      if (p.res) v += us2f(r0[r]);
+      if (p.act) v = leaky(v, 0.01f);
+      if (p.res_post) v += us2f(r1[r]);
+      if (p.res_post2) v += us2f(r2[r]);
+      out[r] = f2us(v);
+    }
+    return out;
+  };
+  if (p.vec_epi == 2 && p.splitk == 1) {
+    // Cout % 8 == 0: lanes l and l^16 (same pixel, adjacent channel groups)
+    // trade one finished fragment each, so every lane owns 8 consecutive
+    // channels and stores 16 bytes. Both lanes of a pair take the same
+    // branches (same pixel; an 8-channel group is in range as a whole).
+    const bool odd = (lane >> 4) & 1;
+    #pragma unroll
+    for (int jp = 0; jp < BFRAG; jp += 2) {
+      const int col0 = n0 + col_base + jp * 16 + ech4;
+      const int col1 = col0 + 16;
+      if (col0 >= p.Cout) continue;
+      const bool ok1 = col1 < p.Cout;
+      floatx4 sc0 = floatx4{1.f, 1.f, 1.f, 1.f}, sc1 = sc0;
+      floatx4 sh0 = floatx4{0.f, 0.f, 0.f, 0.f}, sh1 = sh0;
+      if (p.scale) sc0 = *reinterpret_cast<const floatx4*>(p.scale + col0);
+      if (p.shift) sh0 = *reinterpret_cast<const floatx4*>(p.shift + col0);
+      if (p.scale && ok1)
+        sc1 = *reinterpret_cast<const floatx4*>(p.scale + col1);
+      if (p.shift && ok1)
+        sh1 = *reinterpret_cast<const floatx4*>(p.shift + col1);
       #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long long m = m0 + row_base + i * 16 + erow4 + r;
+      for (int i = 0; i < AFRAG; ++i) {
+        const long long m = m0 + row_base + i * 16 + epix;
         if (m >= p.M) continue;
-        long long idx = m * p.Cout + col;
+        const long long idx0 = m * p.Cout + col0;
+        union { ushortv4 v; unsigned u[2]; } o0, o1, rx;
+        o0.v = finish(acc[i][jp], idx0, sc0, sh0);
+        o1.v = ushortv4{0, 0, 0, 0};
+        if (ok1) o1.v = finish(acc[i][jp + 1], idx0 + 16, sc1, sh1);
+        rx.u[0] = __shfl_xor(odd ? o0.u[0] : o1.u[0], 16, 64);
+        rx.u[1] = __shfl_xor(odd ? o0.u[1] : o1.u[1], 16, 64);
+        union { ushortv8 v; unsigned u[4]; } st;
+        if (!odd) {          // channels col0 .. col0+7
+          st.u[0] = o0.u[0]; st.u[1] = o0.u[1];
+          st.u[2] = rx.u[0]; st.u[3] = rx.u[1];
+          *reinterpret_cast<ushortv8*>(p.y + idx0) = st.v;
+        } else if (ok1) {    // channels col1-4 .. col1+3
+          st.u[0] = rx.u[0]; st.u[1] = rx.u[1];
+          st.u[2] = o1.u[0]; st.u[3] = o1.u[1];
+          *reinterpret_cast<ushortv8*>(p.y + idx0 + 12) = st.v;
+        }
+      }
+    }
+    return;
+  }
+  #pragma unroll
+  for (int j = 0; j < BFRAG; ++j) {
+    const int col = n0 + col_base + j * 16 + ech4;
+    if (col >= p.Cout) continue;
+    if (p.vec_epi) {
+      // Cout % 4 == 0 and col % 4 == 0: the whole group is in range, and
+      // every pointer touched below is aligned for its access (host check)
+      floatx4 sc = floatx4{1.f, 1.f, 1.f, 1.f};
+      floatx4 sh = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (p.splitk == 1) {
+        if (p.scale) sc = *reinterpret_cast<const floatx4*>(p.scale + col);
+        if (p.shift) sh = *reinterpret_cast<const floatx4*>(p.shift + col);
+      }
+      #pragma unroll
+      for (int i = 0; i < AFRAG; ++i) {
+        const long long m = m0 + row_base + i * 16 + epix;
+        if (m >= p.M) continue;
+        const long long idx = m * p.Cout + col;
         if (p.splitk > 1) {
           // each K-split owns a workspace slice: plain stores, no zero-init,
           // no atomics, deterministic sums (combine kernel reduces slices)
-          p.ws[(long long)sk * p.M * p.Cout + idx] = acc[i][j][r];
+          *reinterpret_cast<floatx4*>(ws_slice + idx) = acc[i][j];
+          continue;
+        }
+        *reinterpret_cast<ushortv4*>(p.y + idx) =
+            finish(acc[i][j], idx, sc, sh);
+      }
+      continue;
+    }
+    if (p.pair_epi) {
+      // even Cout (the 50-channel heads): 2-channel groups, 4-byte accesses;
+      // col + r is even, so a pair never straddles Cout
+      #pragma unroll
+      for (int r = 0; r < 4; r += 2) {
+        if (col + r >= p.Cout) continue;
+        const float sc0 = p.scale ? p.scale[col + r] : 1.f;
+        const float sc1 = p.scale ? p.scale[col + r + 1] : 1.f;
+        const float sh0 = p.shift ? p.shift[col + r] : 0.f;
+        const float sh1 = p.shift ? p.shift[col + r + 1] : 0.f;
+        #pragma unroll
+        for (int i = 0; i < AFRAG; ++i) {
+          const long long m = m0 + row_base + i * 16 + epix;
+          if (m >= p.M) continue;
+          const long long idx = m * p.Cout + col + r;
+          if (p.splitk > 1) {
+            *reinterpret_cast<floatx2*>(ws_slice + idx) =
+                floatx2{acc[i][j][r], acc[i][j][r + 1]};
+            continue;
+          }
+          unsigned r0 = 0, r1 = 0, r2 = 0;
+          if (p.res) r0 = *reinterpret_cast<const unsigned*>(p.res + idx);
+          if (p.res_post)
+            r1 = *reinterpret_cast<const unsigned*>(p.res_post + idx);
+          if (p.res_post2)
+            r2 = *reinterpret_cast<const unsigned*>(p.res_post2 + idx);
+          float v0 = acc[i][j][r] * sc0 + sh0;
+          float v1 = acc[i][j][r + 1] * sc1 + sh1;
+          if (p.res) {
+            v0 += us2f((unsigned short)r0); v1 += us2f((unsigned short)(r0 >> 16));
+          }
+          if (p.act) { v0 = leaky(v0, 0.01f); v1 = leaky(v1, 0.01f); }
+          if (p.res_post) {
+            v0 += us2f((unsigned short)r1); v1 += us2f((unsigned short)(r1 >> 16));
+          }
+          if (p.res_post2) {
+            v0 += us2f((unsigned short)r2); v1 += us2f((unsigned short)(r2 >> 16));
+          }
+          *reinterpret_cast<unsigned*>(p.y + idx) =
+              (unsigned)f2us(v0) | ((unsigned)f2us(v1) << 16);
+        }
+      }
+      continue;
+    }
+    // per-element path: odd Cout or an under-aligned operand
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (col + r >= p.Cout) continue;
+      const float sc = p.scale ? p.scale[col + r] : 1.f;
+      const float sh = p.shift ? p.shift[col + r] : 0.f;
+      #pragma unroll
+      for (int i = 0; i < AFRAG; ++i) {
+        const long long m = m0 + row_base + i * 16 + epix;
+        if (m >= p.M) continue;
+        const long long idx = m * p.Cout + col + r;
+        if (p.splitk > 1) {
+          ws_slice[idx] = acc[i][j][r];
           continue;
         }
         float v = acc[i][j][r] * sc + sh;
@@ -378,7 +537,26 @@ a_done:
   }
 }
 
+// One output element of the split-K combine; slices summed s = 0..splitk-1
+// from 0.f so the bits do not depend on which path ran.
+__device__ __forceinline__ float combine_one(float v, float sc, float sh,
+                                             bool has_scale, bool has_res,
+                                             float r0, int act, bool has_rp,
+                                             float r1, bool has_rp2, float r2) {
+  if (has_scale) v = v * sc + sh;
+  if (has_res) v += r0;
+  if (act) v = leaky(v, 0.01f);
+  if (has_rp) v += r1;
+  if (has_rp2) v += r2;
+  return v;
+}
+
 // split-K combine: y = act(scale*ws + shift (+res)) (+res_post...) -> bf16
+// VEC: each thread owns 8 consecutive channels (C % 8 == 0, all pointers
+// 16-byte aligned — host check): two 16-byte loads per slice, 16-byte
+// scale/shift/residual loads, one 16-byte store. The channel-group index is
+// walked incrementally, one 64-bit modulo per thread instead of per element.
+template <bool VEC>
 __global__ void splitk_combine_kernel(const float* __restrict__ ws,
                                       unsigned short* __restrict__ y,
                                       const float* __restrict__ scale,
@@ -388,17 +566,63 @@ __global__ void splitk_combine_kernel(const float* __restrict__ ws,
                                       const unsigned short* __restrict__ res_post2,
                                       long long total, int C, int act,
                                       int splitk) {
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    int c = (int)(i % C);
-    float v = 0.f;
-    for (int s = 0; s < splitk; ++s) v += ws[(long long)s * total + i];
-    if (scale) v = v * scale[c] + shift[c];
-    if (res) v += us2f(res[i]);
-    if (act) v = leaky(v, 0.01f);
-    if (res_post) v += us2f(res_post[i]);
-    if (res_post2) v += us2f(res_post2[i]);
-    y[i] = f2us(v);
+  if constexpr (VEC) {
+    const int C8 = C >> 3;
+    const long long groups = total >> 3;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (g >= groups) return;
+    int c8 = (int)(g % C8);
+    const int cstep = (int)(step % C8);
+    for (; g < groups; g += step) {
+      const long long i = g << 3;
+      floatx4 lo = floatx4{0.f, 0.f, 0.f, 0.f}, hi = lo;
+      for (int s = 0; s < splitk; ++s) {
+        const float* src = ws + (long long)s * total + i;
+        lo += *reinterpret_cast<const floatx4*>(src);
+        hi += *reinterpret_cast<const floatx4*>(src + 4);
+      }
+      floatx4 sc_lo = lo, sc_hi = lo, sh_lo = lo, sh_hi = lo;
+      if (scale) {
+        sc_lo = *reinterpret_cast<const floatx4*>(scale + c8 * 8);
+        sc_hi = *reinterpret_cast<const floatx4*>(scale + c8 * 8 + 4);
+        sh_lo = *reinterpret_cast<const floatx4*>(shift + c8 * 8);
+        sh_hi = *reinterpret_cast<const floatx4*>(shift + c8 * 8 + 4);
+      }
+      ushortv8 r0 = ushortv8{0, 0, 0, 0, 0, 0, 0, 0}, r1 = r0, r2 = r0;
+      if (res) r0 = *reinterpret_cast<const ushortv8*>(res + i);
+      if (res_post) r1 = *reinterpret_cast<const ushortv8*>(res_post + i);
+      if (res_post2) r2 = *reinterpret_cast<const ushortv8*>(res_post2 + i);
+      ushortv8 out;
+      #pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        out[e] = f2us(combine_one(lo[e], sc_lo[e], sh_lo[e], scale != nullptr,
+                                  res != nullptr, us2f(r0[e]), act,
+                                  res_post != nullptr, us2f(r1[e]),
+                                  res_post2 != nullptr, us2f(r2[e])));
+        out[e + 4] = f2us(combine_one(
+            hi[e], sc_hi[e], sh_hi[e], scale != nullptr, res != nullptr,
+            us2f(r0[e + 4]), act, res_post != nullptr, us2f(r1[e + 4]),
+            res_post2 != nullptr, us2f(r2[e + 4])));
+      }
+      *reinterpret_cast<ushortv8*>(y + i) = out;
+      c8 += cstep;
+      if (c8 >= C8) c8 -= C8;
+    }
+  } else {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+         i < total; i += (long long)gridDim.x * blockDim.x) {
+      int c = (int)(i % C);
+      float v = 0.f;
+      for (int s = 0; s < splitk; ++s) v += ws[(long long)s * total + i];
+      v = combine_one(v, scale ? scale[c] : 1.f, scale ? shift[c] : 0.f,
+                      scale != nullptr, res != nullptr,
+                      res ? us2f(res[i]) : 0.f, act, res_post != nullptr,
+                      res_post ? us2f(res_post[i]) : 0.f,
+                      res_post2 != nullptr,
+                      res_post2 ? us2f(res_post2[i]) : 0.f);
+      y[i] = f2us(v);
+    }
   }
 }
 
@@ -532,6 +756,29 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
   } else {
     p.ws = nullptr;
   }
+  // vector epilogue: 4-channel groups need Cout % 4 == 0 (then y, freshly
+  // allocated, and the fp32 slabs are 8-/16-byte aligned at every group) plus
+  // 16-byte scale/shift and 8-byte residual pointers on the unsplit path.
+  // The combine's 8-channel groups need Cout % 8 == 0 and 16 bytes throughout.
+  auto misaligned = [](const void* ptr, uintptr_t a) {
+    return ptr != nullptr && (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0;
+  };
+  p.vec_epi = Cout % 4 == 0 &&
+              (splitk > 1 ||
+               !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
+                 misaligned(p.res, 8) || misaligned(p.res_post, 8) ||
+                 misaligned(p.res_post2, 8) || misaligned(p.y, 8)));
+  if (p.vec_epi && Cout % 8 == 0 && !misaligned(p.y, 16)) p.vec_epi = 2;
+  p.pair_epi = Cout % 2 == 0 &&
+               !(misaligned(p.res, 4) || misaligned(p.res_post, 4) ||
+                 misaligned(p.res_post2, 4) || misaligned(p.y, 4));
+  const bool vec_combine =
+      Cout % 8 == 0 &&
+      !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
+        misaligned(p.res, 16) || misaligned(p.res_post, 16) ||
+        misaligned(p.res_post2, 16) || misaligned(p.y, 16) ||
+        misaligned(p.ws, 16));
+  p.m32 = p.M + BM < (1LL << 31);
   dim3 grid(ntiles * splitk), block(256);
   // short-K blocks (the 1x1 layers: <= 6 chunks) never reach pipeline
   // steady state with single-stage prefetch — use the 2-deep variant there
@@ -560,10 +807,20 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
   }
   if (splitk > 1) {
     long long total = (long long)p.M * Cout;
-    dim3 cgrid(ibp::grid_1d(total, 256, 4096)), cblock(256);
-    hipLaunchKernelGGL(ibp::splitk_combine_kernel, cgrid, cblock, 0, stream,
-                       p.ws, p.y, p.scale, p.shift, p.res, p.res_post,
-                       p.res_post2, total, (int)Cout, p.act, splitk);
+    dim3 cblock(256);
+    if (vec_combine) {
+      dim3 cgrid(ibp::grid_1d(total / 8, 256, 4096));
+      hipLaunchKernelGGL(ibp::splitk_combine_kernel<true>, cgrid, cblock, 0,
+                         stream, p.ws, p.y, p.scale, p.shift, p.res,
+                         p.res_post, p.res_post2, total, (int)Cout, p.act,
+                         splitk);
+    } else {
+      dim3 cgrid(ibp::grid_1d(total, 256, 4096));
+      hipLaunchKernelGGL(ibp::splitk_combine_kernel<false>, cgrid, cblock, 0,
+                         stream, p.ws, p.y, p.scale, p.shift, p.res,
+                         p.res_post, p.res_post2, total, (int)Cout, p.act,
+                         splitk);
+    }
   }
   return y;
 }
