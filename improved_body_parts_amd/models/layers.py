@@ -51,6 +51,17 @@ class Conv(nn.Module):
                                residual_post=residual_post,
                                residual_post2=residual_post2)
 
+    def group_item(self, x, residual_post=None, residual_post2=None):
+        """This module's ``forward(x, ...)`` as a member of
+        ``ops.conv_bn_act_group``: same checks, dropout and training flag."""
+        assert x.size(1) == self.inp_dim, \
+            f"input channel {x.size(1)} does not fit kernel channel {self.inp_dim}"
+        if self.dropout:
+            x = F.dropout(x, p=0.2, training=self.training, inplace=False)
+        return dict(x=x, conv=self.conv, bn=self.bn, act=self.relu is not None,
+                    training=self.training, residual_post=residual_post,
+                    residual_post2=residual_post2)
+
 
 class DilatedConv(nn.Module):
     """Dilated 3x3 conv + BN + LeakyReLU, stride 1 (reference layers_transposed.py:123-155)."""
@@ -259,3 +270,7 @@ class SELayer(nn.Module):
 
     def forward(self, x):
         return ops.se_layer(x, self.fc[0], self.fc[2])
+
+    def group_item(self, x):
+        """``forward(x)`` as a member of ``ops.se_layer_group``."""
+        return (x, self.fc[0], self.fc[2])

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from .. import ops
 from .layers import Conv, Hourglass, SELayer, Backbone
 from .loss import MultiTaskLoss, MultiTaskLossParallel
 
@@ -32,6 +33,9 @@ class Merge(nn.Module):
 
     def forward(self, x, residual=None):
         return self.conv(x, residual_post=residual)
+
+    def group_item(self, x, residual=None):
+        return self.conv.group_item(x, residual_post=residual)
 
 
 class Features(nn.Module):
@@ -107,6 +111,16 @@ class PoseNet(nn.Module):
                 hourglass_feature = [hourglass_feature[0]] + \
                     [hourglass_feature[s] + features_cache[s]
                      for s in range(1, 5)]
+            if not self.training and type(self.features[i]) is Features \
+                    and ops.grouped_heads_enabled(x):
+                # bf16 inference: the heads run one LAYER at a time across the
+                # five scales, each layer as one grouped launch
+                preds_instack, merged = self._heads_grouped(i, hourglass_feature)
+                if merged is not None:
+                    x = x + merged[0]
+                    features_cache = merged
+                pred.append(preds_instack)
+                continue
             features_instack = self.features[i](hourglass_feature)
             preds_instack = []
             for j in range(5):
@@ -120,6 +134,34 @@ class PoseNet(nn.Module):
                     features_cache[j] = merged
             pred.append(preds_instack)
         return pred
+
+    def _heads_grouped(self, i, fms):
+        """Stack i's head layers, scale-parallel: a conv at one scale never
+        depends on a conv at another, so features conv1 x5, conv2 x5, SE x5,
+        outs x5, merge_features x5 and merge_preds x5 (with the
+        merge_features outputs as post-act residuals) each go out as one
+        grouped launch. Members come from the modules' own ``group_item``
+        (their checks, dropout and training flags apply as in ``forward``)
+        and run the same kernels, plans and operands as the per-scale loop in
+        ``forward`` — the outputs are bit-identical.
+        Returns (preds, merged or None for the last stack)."""
+        assert len(fms) == 5, f"hourglass produced {len(fms)} scales, expected 5"
+
+        group = ops.conv_bn_act_group
+        heads = self.features[i].before_regress
+        f = group([heads[j][0].group_item(fms[j]) for j in range(5)])
+        f = group([heads[j][1].group_item(f[j]) for j in range(5)])
+        f = ops.se_layer_group([heads[j][2].group_item(f[j])
+                                for j in range(5)])
+        preds = group([self.outs[i][j].group_item(f[j]) for j in range(5)])
+        if i == self.nstack - 1:
+            return preds, None
+        mf = group([self.merge_features[i][j].group_item(f[j])
+                    for j in range(5)])
+        merged = group([self.merge_preds[i][j].group_item(preds[j],
+                                                          residual=mf[j])
+                        for j in range(5)])
+        return preds, merged
 
     def _initialize_weights(self):
         for m in self.modules():

@@ -80,6 +80,46 @@ def conv_bn_add_act(x, conv, bn, residual, act: bool, training: bool,
     return y
 
 
+def conv_bn_act_group(items):
+    """Several INDEPENDENT :func:`conv_bn_act` / :func:`conv_bn_add_act`
+    calls — ``items`` is a list of dicts with keys ``x conv bn act`` and
+    optionally ``residual residual_post residual_post2 training`` — returning
+    their outputs in order. On the HIP bf16 inference path the members share
+    one grouped kernel launch per 8 (see ``conv.conv_bn_act_group_hip``);
+    elsewhere they run one by one. Results never depend on the grouping."""
+    if items and all(use_hip_for(it["x"]) for it in items):
+        from . import conv as _conv
+        return _conv.conv_bn_act_group_hip(items)
+    out = []
+    for it in items:
+        if it.get("residual") is not None:
+            y = conv_bn_add_act(
+                it["x"], it["conv"], it["bn"], it["residual"], act=it["act"],
+                training=it.get("training", False),
+                residual_post=it.get("residual_post"))
+            if it.get("residual_post2") is not None:
+                y = y + it["residual_post2"]
+            out.append(y)
+        else:
+            out.append(conv_bn_act(
+                it["x"], it["conv"], it["bn"], act=it["act"],
+                training=it.get("training", False),
+                residual_post=it.get("residual_post"),
+                residual_post2=it.get("residual_post2")))
+    return out
+
+
+def grouped_heads_enabled(x) -> bool:
+    """True when the per-scale head layers may be issued as grouped launches:
+    HIP backend, bf16, grad disabled, ``IBP_CONV_GROUP`` not ``0`` (read at
+    call time)."""
+    if not (use_hip_for(x) and x.dtype == torch.bfloat16
+            and not torch.is_grad_enabled()):
+        return False
+    from . import conv as _conv
+    return _conv.conv_group_enabled()
+
+
 # ---------------------------------------------------------------------------
 # pooling / upsampling / concat
 # ---------------------------------------------------------------------------
@@ -118,6 +158,16 @@ def se_layer(x, fc1, fc2):
     y = F.leaky_relu(fc1(y.to(x.dtype)), LEAKY_SLOPE)
     y = torch.sigmoid(fc2(y))
     return x * y.view(n, c, 1, 1)
+
+
+def se_layer_group(items):
+    """:func:`se_layer` over independent maps — ``items`` is a list of
+    ``(x, fc1, fc2)``; one grouped launch per SE stage on the HIP inference
+    path, per-member calls elsewhere."""
+    if items and all(use_hip_for(x) for x, _, _ in items):
+        from . import spatial
+        return spatial.se_layer_group_hip(items)
+    return [se_layer(x, fc1, fc2) for x, fc1, fc2 in items]
 
 
 # ---------------------------------------------------------------------------

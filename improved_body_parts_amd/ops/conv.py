@@ -76,6 +76,26 @@ def _bias_fold(weight, bias):
     return scale, shift
 
 
+def _inference_epilogue(weight, bias, gamma, beta, bn_mod):
+    """(scale, shift) of the conv kernel's fused epilogue on the inference
+    path: the folded eval-mode BN (cached on the BN module against the
+    parameter versions), else the bias-only pair, else (None, None)."""
+    if gamma is not None:
+        ver = (gamma._version, bn_mod.running_mean._version,
+               bn_mod.running_var._version)
+        cached = getattr(bn_mod, "_ibp_folded", None)
+        if cached is not None and cached[0] == ver:
+            return cached[1], cached[2]
+        invstd = torch.rsqrt(bn_mod.running_var.float() + bn_mod.eps)
+        scale = gamma.float() * invstd
+        shift = beta.float() - bn_mod.running_mean.float() * scale
+        bn_mod._ibp_folded = (ver, scale, shift)
+        return scale, shift
+    if bias is not None:
+        return _bias_fold(weight, bias)
+    return None, None
+
+
 def _tick_running_stats(bn_mod):
     """The finalize kernel updates running stats in place without going
     through ATen — tick their version counters so the eval-path folded-BN
@@ -102,20 +122,8 @@ class ConvBnActFn(torch.autograd.Function):
         # inside Function.forward, so torch.is_grad_enabled() can't be used here.
         if inference and x.dtype == torch.bfloat16:
             from . import conv_kernels
-            if gamma is not None:
-                # cache the folded scale/shift on the BN module
-                ver = (gamma._version, bn_mod.running_mean._version,
-                       bn_mod.running_var._version)
-                cached = getattr(bn_mod, "_ibp_folded", None)
-                if cached is not None and cached[0] == ver:
-                    scale, shift = cached[1], cached[2]
-                else:
-                    invstd = torch.rsqrt(bn_mod.running_var.float() + bn_mod.eps)
-                    scale = gamma.float() * invstd
-                    shift = beta.float() - bn_mod.running_mean.float() * scale
-                    bn_mod._ibp_folded = (ver, scale, shift)
-            elif bias is not None:
-                scale, shift = _bias_fold(weight, bias)
+            scale, shift = _inference_epilogue(weight, bias, gamma, beta,
+                                               bn_mod)
             if scale is not None or act or residual is not None \
                     or residual_post is not None:
                 y = conv_kernels.conv_fwd(x, weight, stride, padding, dilation,
@@ -276,3 +284,56 @@ def conv_bn_act_hip(x, conv, bn, act: bool, residual=None, training: bool = Fals
         residual_post, residual_post2,
         conv.stride, conv.padding, conv.dilation, act,
         bn_training, bn, inference)
+
+
+def conv_group_enabled() -> bool:
+    """``IBP_CONV_GROUP=0`` (read at call time) restores one launch per conv
+    for A/B runs."""
+    import os
+    return os.environ.get("IBP_CONV_GROUP", "1") != "0"
+
+
+def conv_bn_act_group_hip(items):
+    """Independent Conv(+BN)(+LeakyReLU)(+residuals) modules in one grouped
+    launch per 8 members. ``items`` is a list of dicts with keys ``x conv bn
+    act`` and optionally ``residual residual_post residual_post2 training``.
+
+    Only the bf16 inference fast path is grouped (grad disabled, BN in eval
+    mode, every member inside the MFMA envelope); otherwise every member goes
+    through :func:`conv_bn_act_hip` on its own. Outputs are bit-identical
+    either way: a grouped member runs the plan it would get alone."""
+    def single(it):
+        return conv_bn_act_hip(it["x"], it["conv"], it["bn"], it["act"],
+                               residual=it.get("residual"),
+                               training=it.get("training", False),
+                               residual_post=it.get("residual_post"),
+                               residual_post2=it.get("residual_post2"))
+
+    groupable = len(items) > 1 and conv_group_enabled() \
+        and not torch.is_grad_enabled()
+    members = []
+    if groupable:
+        from . import conv_kernels
+        for it in items:
+            bn = it["bn"]
+            if it["x"].dtype != torch.bfloat16 or \
+                    (it.get("training", False) and bn is not None
+                     and bn.training):
+                groupable = False
+                break
+            conv = it["conv"]
+            scale, shift = _inference_epilogue(
+                conv.weight, conv.bias,
+                bn.weight if bn is not None else None,
+                bn.bias if bn is not None else None, bn)
+            members.append(dict(
+                x=_to_cl(it["x"]), weight=conv.weight, stride=conv.stride,
+                padding=conv.padding, dilation=conv.dilation, scale=scale,
+                shift=shift, residual=it.get("residual"), act=it["act"],
+                residual_post=it.get("residual_post"),
+                residual_post2=it.get("residual_post2")))
+    if groupable:
+        ys = conv_kernels.conv_fwd_group(members)
+        if ys is not None:
+            return ys
+    return [single(it) for it in items]

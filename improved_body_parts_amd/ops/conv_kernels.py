@@ -235,6 +235,46 @@ def conv_fwd(x, weight, stride, padding, dilation,
     return y.permute(0, 3, 1, 2)  # NHWC buffer -> NCHW view (channels_last)
 
 
+def conv_fwd_group(members):
+    """Several INDEPENDENT conv forwards in one grouped launch per 8 members
+    (plus one grouped split-K combine). ``members`` is a list of dicts with
+    the :func:`conv_fwd` arguments (``x weight stride padding dilation`` and
+    the optional ``scale shift residual act residual_post residual_post2``).
+    Every member runs the plan it would get alone, so each output equals the
+    single call bit for bit. Returns the outputs in order, or ``None`` when a
+    member is outside the grouped envelope (the caller then issues the
+    members one by one)."""
+    ext = hip_extension()
+    xs, packs, geom = [], [], []
+    scales, shifts, ress, acts, posts, post2s = [], [], [], [], [], []
+    for m in members:
+        x, weight = m["x"], m["weight"]
+        stride, padding, dilation = m["stride"], m["padding"], m["dilation"]
+        if not _supported(x, weight, stride, padding, dilation) \
+                or _is_stem(x, weight, stride, padding, dilation):
+            return None
+        x = x.contiguous(memory_format=_CL)
+        n, cin, h, w_ = x.shape
+        cout, _, kh, kw = weight.shape
+        ho = (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
+        wo = (w_ + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
+        xs.append(x)
+        packs.append(packed_weight(weight))
+        geom.append([n, h, w_, cin, cout, kh, kw, stride[0], padding[0],
+                     padding[1], dilation[0], dilation[1], ho, wo, 1])
+        scales.append(m.get("scale"))
+        shifts.append(m.get("shift"))
+        acts.append(1 if m.get("act") else 0)
+        for lst, key in ((ress, "residual"), (posts, "residual_post"),
+                         (post2s, "residual_post2")):
+            r = m.get(key)
+            lst.append(r.contiguous(memory_format=_CL) if r is not None
+                       else None)
+    ys = ext.conv_mfma_fwd_grouped(xs, packs, geom, scales, shifts, ress,
+                                   acts, posts, post2s)
+    return [y.permute(0, 3, 1, 2) for y in ys]
+
+
 def conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
     """dx = stride-1 conv of the (virtually) zero-dilated dy with 180-rotated
     transposed weights; pad' = dil*(K-1) - pad, gather stride zs = stride."""

@@ -40,6 +40,12 @@ Tensor se_scale(const Tensor& x, const Tensor& s, const c10::optional<Tensor>& a
 Tensor se_gate(const Tensor& pooled, const Tensor& w1, const Tensor& b1,
                const Tensor& w2, const Tensor& b2, double slope,
                double pool_scale);
+std::vector<Tensor> se_layer_grouped(const std::vector<Tensor>& xs,
+                                     const std::vector<Tensor>& w1s,
+                                     const std::vector<Tensor>& b1s,
+                                     const std::vector<Tensor>& w2s,
+                                     const std::vector<Tensor>& b2s,
+                                     double slope);
 
 // loss.hip
 Tensor focal_l2_fwd(const Tensor& pred, const Tensor& gt, const Tensor& mask,
@@ -60,6 +66,18 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
                      const c10::optional<Tensor>& residual, bool act,
                      const c10::optional<Tensor>& residual_post,
                      const c10::optional<Tensor>& residual_post2, int64_t zs);
+
+std::vector<Tensor> conv_mfma_fwd_grouped(
+    const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
+    const std::vector<std::vector<int64_t>>& geom,
+    const std::vector<c10::optional<Tensor>>& scales,
+    const std::vector<c10::optional<Tensor>>& shifts,
+    const std::vector<c10::optional<Tensor>>& residuals,
+    const std::vector<int64_t>& acts,
+    const std::vector<c10::optional<Tensor>>& residual_posts,
+    const std::vector<c10::optional<Tensor>>& residual_post2s);
+
+std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K);
 
 void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
                       const c10::optional<Tensor>& dgrad_pack);
@@ -107,6 +125,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_gate", &se_gate, "fused GAP-gate: sigmoid(W2@leaky(W1@p+b1)+b2)",
         py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
         py::arg("b2"), py::arg("slope"), py::arg("pool_scale") = 1.0);
+  m.def("se_layer_grouped", &se_layer_grouped,
+        "inference SE layers of independent maps: one launch per stage");
   m.def("focal_l2_fwd", &focal_l2_fwd);
   m.def("focal_l2_bwd", &focal_l2_bwd);
   m.def("conv_mfma_fwd", &conv_mfma_fwd, "MFMA implicit-GEMM conv forward",
@@ -118,6 +138,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("residual") = c10::nullopt, py::arg("act") = false,
         py::arg("residual_post") = c10::nullopt,
         py::arg("residual_post2") = c10::nullopt, py::arg("zs") = 1);
+  m.def("conv_mfma_fwd_grouped", &conv_mfma_fwd_grouped,
+        "independent MFMA convs in one grouped launch per 8 (+ one combine)",
+        py::arg("xs"), py::arg("ws_packed"), py::arg("geom"),
+        py::arg("scales"), py::arg("shifts"), py::arg("residuals"),
+        py::arg("acts"), py::arg("residual_posts"),
+        py::arg("residual_post2s"));
+  m.def("conv_mfma_tile_plan", &conv_mfma_tile_plan,
+        "debug: [BM, BN, splitk, deep] planned for GEMM extents (M, Cout, K)",
+        py::arg("M"), py::arg("Cout"), py::arg("K"));
   m.def("pack_conv_weight", &pack_conv_weight,
         "fwd + dgrad weight packs in one kernel",
         py::arg("w"), py::arg("fwd_pack"), py::arg("dgrad_pack") = c10::nullopt);

@@ -31,7 +31,11 @@
 // 50-channel merge heads) and via the elementwise tail, stride 1 or 2.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <algorithm>
+#include <cstddef>
 #include <cstdlib>
+#include <type_traits>
+#include <vector>
 #include "common.h"
 
 namespace ibp {
@@ -78,18 +82,22 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 // DEEP: two-stage register prefetch — wins ONLY on short-K shapes (the 1x1
 // layers at <= 6 K-chunks never reach pipeline steady state); on long-K 3x3
 // shapes the extra register bank measured 10-15% slower.
-template <int BM, int BN, bool DEEP = false>
-__global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
-  __shared__ unsigned short lds_a[2][BM * BK];
-  __shared__ unsigned short lds_b[2][BN * BK];
-
+//
+// The body is a device function so that the single-problem kernels and the
+// grouped kernel (several independent convs in one launch) share it: `bid`
+// is the block id LOCAL to this problem, lds_a/lds_b hold 2*BM*BK and
+// 2*BN*BK shorts (double buffer).
+template <int BM, int BN, bool DEEP, typename Params>
+__device__ __forceinline__ void conv_mfma_body(const Params& p,
+                                               const int bid,
+                                               unsigned short* lds_a,
+                                               unsigned short* lds_b) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
 
   // tile coordinates; with split-K, a tile's K-slices are adjacent block ids
   const int ntiles_n = (p.Cout + BN - 1) / BN;
-  int bid = blockIdx.x;
   const int sk = bid % p.splitk;
   const int tile = bid / p.splitk;
   const int mt = tile / ntiles_n;
@@ -293,11 +301,11 @@ a_done:
                          unsigned short (&b_reg)[B_ELEMS]) {
     #pragma unroll
     for (int v = 0; v < A_ELEMS / 8; ++v)
-      *reinterpret_cast<ushortv8*>(&lds_a[buf][lds_off(a_row, a_off + v * 8)]) =
+      *reinterpret_cast<ushortv8*>(&lds_a[buf * (BM * BK) + lds_off(a_row, a_off + v * 8)]) =
           *reinterpret_cast<const ushortv8*>(&a_reg[v * 8]);
     #pragma unroll
     for (int v = 0; v < B_ELEMS / 8; ++v)
-      *reinterpret_cast<ushortv8*>(&lds_b[buf][lds_off(b_row, b_off + v * 8)]) =
+      *reinterpret_cast<ushortv8*>(&lds_b[buf * (BN * BK) + lds_off(b_row, b_off + v * 8)]) =
           *reinterpret_cast<const ushortv8*>(&b_reg[v * 8]);
   };
 
@@ -311,11 +319,11 @@ a_done:
       #pragma unroll
       for (int i = 0; i < AFRAG; ++i)
         afrag[i] = *reinterpret_cast<const short8*>(
-            &lds_a[buf][lds_off(row_base + i * 16 + l15, kk + kslice)]);
+            &lds_a[buf * (BM * BK) + lds_off(row_base + i * 16 + l15, kk + kslice)]);
       #pragma unroll
       for (int j = 0; j < BFRAG; ++j)
         bfrag[j] = *reinterpret_cast<const short8*>(
-            &lds_b[buf][lds_off(col_base + j * 16 + l15, kk + kslice)]);
+            &lds_b[buf * (BN * BK) + lds_off(col_base + j * 16 + l15, kk + kslice)]);
       // weight fragment FIRST: D[row][col] is then (channel, pixel), which
       // gives each lane 4 consecutive channels of one pixel (see epilogue)
       #pragma unroll
@@ -537,6 +545,98 @@ a_done:
   }
 }
 
+template <int BM, int BN, bool DEEP = false>
+__global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
+  __shared__ unsigned short lds_a[2 * BM * BK];
+  __shared__ unsigned short lds_b[2 * BN * BK];
+  conv_mfma_body<BM, BN, DEEP>(p, blockIdx.x, lds_a, lds_b);
+}
+
+// ---- grouped launch --------------------------------------------------------
+// Up to kMaxGroup INDEPENDENT convs in one grid. The problem table rides the
+// kernel arguments; block_end[i] is the exclusive prefix sum of the problems'
+// block counts, so a block finds its problem with a scan of at most
+// kMaxGroup - 1 uniform compares, then runs the <BM,BN,DEEP> body that the
+// problem would get alone, with a problem-local block id. Every block writes
+// only its own problem's outputs, so the order of problems in the grid never
+// changes a result; the host puts the blocks with the most K-chunks first.
+constexpr int kMaxGroup = 8;
+
+struct ConvGroupParams {
+  ConvParams p[kMaxGroup];
+  int block_end[kMaxGroup];
+  int cfg[kMaxGroup];        // tile_cfg(BM, BN, deep)
+  int n;
+};
+
+// tile configuration index shared by host and device
+constexpr int tile_cfg(int BM, int BN, bool deep) {
+  return ((BM == 128 ? (BN == 128 ? 0 : 1) : (BM == 64 ? 2 : 3)) << 1) |
+         (deep ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
+    ConvGroupParams g) {
+  // one static buffer sized for the largest tile (128x128: 2 x 32 KB); the
+  // smaller configurations carve their lds_a / lds_b out of its front
+  __shared__ __attribute__((aligned(16))) unsigned short lds[4 * 128 * BK];
+  const int gb = blockIdx.x;
+  int pi = 0, base = 0, cfg = g.cfg[0];
+  #pragma unroll
+  for (int i = 0; i < kMaxGroup - 1; ++i) {
+    if (i + 1 < g.n && gb >= g.block_end[i]) {
+      pi = i + 1;
+      base = g.block_end[i];
+      cfg = g.cfg[i + 1];
+    }
+  }
+  // A dynamic index into a by-value kernel argument makes the compiler keep
+  // a private copy of the whole table (1.5 KB of scratch per lane). Read the
+  // chosen entry straight from the kernel-argument segment instead — `g` is
+  // the only argument, so it starts at offset 0 — which stays scalar loads
+  // with a uniform offset.
+  typedef __attribute__((address_space(4))) const char* kernarg_bytes;
+  kernarg_bytes ka = (kernarg_bytes)__builtin_amdgcn_kernarg_segment_ptr();
+  typedef __attribute__((address_space(4))) const ConvParams* kernarg_params;
+  const auto& p = *(kernarg_params)(ka + offsetof(ConvGroupParams, p) +
+                                    (size_t)pi * sizeof(ConvParams));
+  const int bid = gb - base;
+  switch (cfg) {
+    case tile_cfg(128, 128, false):
+      conv_mfma_body<128, 128, false>(p, bid, lds, lds + 2 * 128 * BK); break;
+    case tile_cfg(128, 128, true):
+      conv_mfma_body<128, 128, true>(p, bid, lds, lds + 2 * 128 * BK); break;
+    case tile_cfg(128, 64, false):
+      conv_mfma_body<128, 64, false>(p, bid, lds, lds + 2 * 128 * BK); break;
+    case tile_cfg(128, 64, true):
+      conv_mfma_body<128, 64, true>(p, bid, lds, lds + 2 * 128 * BK); break;
+    case tile_cfg(64, 64, false):
+      conv_mfma_body<64, 64, false>(p, bid, lds, lds + 2 * 64 * BK); break;
+    case tile_cfg(64, 64, true):
+      conv_mfma_body<64, 64, true>(p, bid, lds, lds + 2 * 64 * BK); break;
+    case tile_cfg(32, 64, false):
+      conv_mfma_body<32, 64, false>(p, bid, lds, lds + 2 * 32 * BK); break;
+    default:
+      conv_mfma_body<32, 64, true>(p, bid, lds, lds + 2 * 32 * BK); break;
+  }
+}
+
+// The grouped kernel reads its table at offset 0 of the kernel-argument
+// segment: it must stay the kernel's ONLY explicit argument (explicit
+// arguments come first in the segment, hidden ones after), with the problem
+// array leading the struct.
+static_assert(std::is_same<decltype(&conv_mfma_grouped_kernel),
+                           void (*)(ConvGroupParams)>::value,
+              "conv_mfma_grouped_kernel must take the table as its only "
+              "argument: it is read at kernarg offset 0");
+static_assert(offsetof(ConvGroupParams, p) == 0 &&
+                  std::is_standard_layout<ConvGroupParams>::value &&
+                  std::is_trivially_copyable<ConvGroupParams>::value &&
+                  sizeof(ConvParams) % alignof(ConvParams) == 0 &&
+                  sizeof(ConvGroupParams) <= 4096,
+              "ConvGroupParams layout: problem array first, within the "
+              "kernel-argument limit");
+
 // One output element of the split-K combine; slices summed s = 0..splitk-1
 // from 0.f so the bits do not depend on which path ran.
 __device__ __forceinline__ float combine_one(float v, float sc, float sh,
@@ -556,21 +656,21 @@ __device__ __forceinline__ float combine_one(float v, float sc, float sh,
 // 16-byte aligned — host check): two 16-byte loads per slice, 16-byte
 // scale/shift/residual loads, one 16-byte store. The channel-group index is
 // walked incrementally, one 64-bit modulo per thread instead of per element.
+// `bid` / `nblocks` are the block id and block count LOCAL to this problem
+// (the grouped combine runs several problems in one grid).
 template <bool VEC>
-__global__ void splitk_combine_kernel(const float* __restrict__ ws,
-                                      unsigned short* __restrict__ y,
-                                      const float* __restrict__ scale,
-                                      const float* __restrict__ shift,
-                                      const unsigned short* __restrict__ res,
-                                      const unsigned short* __restrict__ res_post,
-                                      const unsigned short* __restrict__ res_post2,
-                                      long long total, int C, int act,
-                                      int splitk) {
+__device__ __forceinline__ void splitk_combine_body(
+    const float* __restrict__ ws, unsigned short* __restrict__ y,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const unsigned short* __restrict__ res,
+    const unsigned short* __restrict__ res_post,
+    const unsigned short* __restrict__ res_post2, long long total, int C,
+    int act, int splitk, int bid, int nblocks) {
   if constexpr (VEC) {
     const int C8 = C >> 3;
     const long long groups = total >> 3;
-    const long long step = (long long)gridDim.x * blockDim.x;
-    long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long step = (long long)nblocks * blockDim.x;
+    long long g = bid * (long long)blockDim.x + threadIdx.x;
     if (g >= groups) return;
     int c8 = (int)(g % C8);
     const int cstep = (int)(step % C8);
@@ -610,8 +710,8 @@ __global__ void splitk_combine_kernel(const float* __restrict__ ws,
       if (c8 >= C8) c8 -= C8;
     }
   } else {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-         i < total; i += (long long)gridDim.x * blockDim.x) {
+    for (long long i = bid * (long long)blockDim.x + threadIdx.x;
+         i < total; i += (long long)nblocks * blockDim.x) {
       int c = (int)(i % C);
       float v = 0.f;
       for (int s = 0; s < splitk; ++s) v += ws[(long long)s * total + i];
@@ -624,6 +724,64 @@ __global__ void splitk_combine_kernel(const float* __restrict__ ws,
       y[i] = f2us(v);
     }
   }
+}
+
+template <bool VEC>
+__global__ void splitk_combine_kernel(const float* __restrict__ ws,
+                                      unsigned short* __restrict__ y,
+                                      const float* __restrict__ scale,
+                                      const float* __restrict__ shift,
+                                      const unsigned short* __restrict__ res,
+                                      const unsigned short* __restrict__ res_post,
+                                      const unsigned short* __restrict__ res_post2,
+                                      long long total, int C, int act,
+                                      int splitk) {
+  splitk_combine_body<VEC>(ws, y, scale, shift, res, res_post, res_post2,
+                           total, C, act, splitk, (int)blockIdx.x,
+                           (int)gridDim.x);
+}
+
+// grouped combine: the split members of one grouped conv launch, same
+// block -> problem table scheme; each problem keeps the grid size and the
+// <VEC> arithmetic it has alone.
+struct CombineProblem {
+  const float* ws;
+  unsigned short* y;
+  const float* scale;
+  const float* shift;
+  const unsigned short* res;
+  const unsigned short* res_post;
+  const unsigned short* res_post2;
+  long long total;
+  int C, act, splitk, vec;
+};
+
+struct CombineGroupParams {
+  CombineProblem c[kMaxGroup];
+  int block_end[kMaxGroup];
+  int n;
+};
+
+__global__ void splitk_combine_grouped_kernel(CombineGroupParams g) {
+  const int gb = blockIdx.x;
+  int pi = 0, base = 0;
+  #pragma unroll
+  for (int i = 0; i < kMaxGroup - 1; ++i) {
+    if (i + 1 < g.n && gb >= g.block_end[i]) {
+      pi = i + 1;
+      base = g.block_end[i];
+    }
+  }
+  const CombineProblem& c = g.c[pi];
+  const int nblocks = g.block_end[pi] - base;
+  if (c.vec)
+    splitk_combine_body<true>(c.ws, c.y, c.scale, c.shift, c.res, c.res_post,
+                              c.res_post2, c.total, c.C, c.act, c.splitk,
+                              gb - base, nblocks);
+  else
+    splitk_combine_body<false>(c.ws, c.y, c.scale, c.shift, c.res, c.res_post,
+                               c.res_post2, c.total, c.C, c.act, c.splitk,
+                               gb - base, nblocks);
 }
 
 // weight pack: [Cout,Cin,KH,KW] (standard contiguous) -> fwd [Cout][f*Cin+ci]
@@ -676,18 +834,89 @@ void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
       Cout, Cin, KH, KW);
 }
 
-Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
-                     int64_t H, int64_t W, int64_t Cin, int64_t Cout,
-                     int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
-                     int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
-                     int64_t Wo, const c10::optional<Tensor>& scale,
-                     const c10::optional<Tensor>& shift,
-                     const c10::optional<Tensor>& residual, bool act,
-                     const c10::optional<Tensor>& residual_post,
-                     const c10::optional<Tensor>& residual_post2, int64_t zs) {
+namespace {
+
+// Everything conv_mfma_fwd decides before launching: the filled ConvParams
+// (all but the workspace pointer), the tile, the split and the epilogue
+// paths. The single and the grouped entry both launch from this plan, so a
+// member of a group runs exactly what it would run alone.
+struct ConvPlan {
+  ibp::ConvParams p;
+  Tensor y;
+  int BM, BN;
+  bool deep;
+  bool vec_combine;    // before the workspace is known: all BUT its alignment
+  int nblocks;         // ntiles * splitk
+  int nk_block;        // K-chunks per block
+  long long ws_elems;  // fp32 workspace elements (0 when unsplit)
+};
+
+bool misaligned(const void* ptr, uintptr_t a) {
+  return ptr != nullptr && (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0;
+}
+
+// Tile and split-K choice: a function of the GEMM extents alone (and the
+// IBP_CONV_BM / IBP_SPLITK_TARGET overrides), so it can be queried without
+// tensors (conv_mfma_tile_plan below, used by the tests).
+struct TilePlan {
+  int BM, BN, n_mtiles, ntiles, splitk, nk_block;
+  bool deep;
+};
+
+TilePlan plan_tile(long long M, int Cout, int K) {
+  TilePlan t;
+  // ---- tile selection -------------------------------------------------------
+  // BM: small-M tiles for the hourglass's 8^2/16^2 scales (avoids the 8-16x
+  // split-K workspace round-trip measured in round 1); BN: minimise padded
+  // cols (Cout=192 as 3x64 beats 2x128 — half the second 128-tile is wasted).
+  int BM = 128;
+  if (M <= 2048) BM = 32;
+  else if (M <= 8192) BM = 64;
+  if (const char* e = getenv("IBP_CONV_BM")) BM = atoi(e);
+  const long long padded128 = ((Cout + 127) / 128) * 128LL;
+  const long long padded64 = ((Cout + 63) / 64) * 64LL;
+  int BN = (BM == 128 && Cout > 64 && padded128 <= padded64) ? 128 : 64;
+  t.n_mtiles = (int)((M + BM - 1) / BM);
+  const int ntiles = t.n_mtiles * (int)((Cout + BN - 1) / BN);
+  const int nk_total = (K + ibp::BK - 1) / ibp::BK;
+  // split K on small grids so the 256-CU chip stays filled (~2 blocks/CU).
+  // Normalise so EVERY slice has work: with raw splitk=7 over nk_total=8 the
+  // last 3 slices get no chunks, return early, and the combine kernel then
+  // sums their UNINITIALISED workspace slices (silent garbage whenever the
+  // allocator hands back dirty memory — found as exploding gradients through
+  // the scale-2 Merge convs, scripts/diag_splitk.py).
+  int sk_target = 384;
+  if (const char* e = getenv("IBP_SPLITK_TARGET")) sk_target = atoi(e);
+  int splitk = 1;
+  if (ntiles < sk_target && nk_total > 1) {
+    splitk = std::min((int)nk_total, (sk_target + ntiles - 1) / ntiles);
+    int nk_chunk = ((int)nk_total + splitk - 1) / splitk;
+    splitk = ((int)nk_total + nk_chunk - 1) / nk_chunk;
+  }
+  t.BM = BM;
+  t.BN = BN;
+  t.ntiles = ntiles;
+  t.splitk = splitk;
+  // short-K blocks (the 1x1 layers: <= 6 chunks) never reach pipeline
+  // steady state with single-stage prefetch — use the 2-deep variant there
+  t.nk_block = (nk_total + splitk - 1) / splitk;
+  t.deep = t.nk_block <= 6;
+  return t;
+}
+
+ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
+                   int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                   int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
+                   int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
+                   int64_t Wo, const c10::optional<Tensor>& scale,
+                   const c10::optional<Tensor>& shift,
+                   const c10::optional<Tensor>& residual, bool act,
+                   const c10::optional<Tensor>& residual_post,
+                   const c10::optional<Tensor>& residual_post2, int64_t zs) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::ScalarType::BFloat16);
   TORCH_CHECK(w_packed.is_contiguous());
-  ibp::ConvParams p;
+  ConvPlan plan;
+  ibp::ConvParams& p = plan.p;
   p.x = reinterpret_cast<const unsigned short*>(x.data_ptr());
   p.w = reinterpret_cast<const unsigned short*>(w_packed.data_ptr());
   p.scale = scale.has_value() ? scale->data_ptr<float>() : nullptr;
@@ -713,56 +942,21 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
   p.act = act ? 1 : 0;
   // any Cin is legal: subpieces crossing tap boundaries take the per-element
   // re-derive path (the Cin=3 stem runs there; Cin % 8 == 0 stays vectorized)
-  Tensor y = torch::empty({N, Ho, Wo, Cout}, x.options());
-  p.y = reinterpret_cast<unsigned short*>(y.data_ptr());
-  auto stream = at::hip::getCurrentHIPStream().stream();
+  plan.y = torch::empty({N, Ho, Wo, Cout}, x.options());
+  p.y = reinterpret_cast<unsigned short*>(plan.y.data_ptr());
 
-  // ---- tile selection -------------------------------------------------------
-  // BM: small-M tiles for the hourglass's 8^2/16^2 scales (avoids the 8-16x
-  // split-K workspace round-trip measured in round 1); BN: minimise padded
-  // cols (Cout=192 as 3x64 beats 2x128 — half the second 128-tile is wasted).
-  int BM = 128;
-  if (p.M <= 2048) BM = 32;
-  else if (p.M <= 8192) BM = 64;
-  if (const char* e = getenv("IBP_CONV_BM")) BM = atoi(e);
-  const long long padded128 = ((Cout + 127) / 128) * 128LL;
-  const long long padded64 = ((Cout + 63) / 64) * 64LL;
-  int BN = (BM == 128 && Cout > 64 && padded128 <= padded64) ? 128 : 64;
-  p.n_mtiles = (int)((p.M + BM - 1) / BM);
-  const int ntiles = p.n_mtiles * (int)((Cout + BN - 1) / BN);
-  const int nk_total = (p.K + ibp::BK - 1) / ibp::BK;
-  // split K on small grids so the 256-CU chip stays filled (~2 blocks/CU).
-  // Normalise so EVERY slice has work: with raw splitk=7 over nk_total=8 the
-  // last 3 slices get no chunks, return early, and the combine kernel then
-  // sums their UNINITIALISED workspace slices (silent garbage whenever the
-  // allocator hands back dirty memory — found as exploding gradients through
-  // the scale-2 Merge convs, scripts/diag_splitk.py).
-  int sk_target = 384;
-  if (const char* e = getenv("IBP_SPLITK_TARGET")) sk_target = atoi(e);
-  int splitk = 1;
-  if (ntiles < sk_target && nk_total > 1) {
-    splitk = std::min((int)nk_total, (sk_target + ntiles - 1) / ntiles);
-    int nk_chunk = ((int)nk_total + splitk - 1) / splitk;
-    splitk = ((int)nk_total + nk_chunk - 1) / nk_chunk;
-  }
+  const TilePlan t = plan_tile(p.M, p.Cout, p.K);
+  const int BM = t.BM, BN = t.BN, splitk = t.splitk;
+  p.n_mtiles = t.n_mtiles;
   p.splitk = splitk;
-  Tensor ws;
-  if (splitk > 1) {
-    // per-split slices written with plain stores -> empty() is safe (every
-    // in-range element is covered by every split's epilogue)
-    ws = torch::empty({(long long)splitk * p.M * Cout},
-                      x.options().dtype(torch::kFloat32));
-    p.ws = ws.data_ptr<float>();
-  } else {
-    p.ws = nullptr;
-  }
+  // per-split slices written with plain stores -> an uninitialised workspace
+  // is safe (every in-range element is covered by every split's epilogue)
+  plan.ws_elems = splitk > 1 ? (long long)splitk * p.M * Cout : 0;
+  p.ws = nullptr;
   // vector epilogue: 4-channel groups need Cout % 4 == 0 (then y, freshly
   // allocated, and the fp32 slabs are 8-/16-byte aligned at every group) plus
   // 16-byte scale/shift and 8-byte residual pointers on the unsplit path.
   // The combine's 8-channel groups need Cout % 8 == 0 and 16 bytes throughout.
-  auto misaligned = [](const void* ptr, uintptr_t a) {
-    return ptr != nullptr && (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0;
-  };
   p.vec_epi = Cout % 4 == 0 &&
               (splitk > 1 ||
                !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
@@ -772,18 +966,36 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
   p.pair_epi = Cout % 2 == 0 &&
                !(misaligned(p.res, 4) || misaligned(p.res_post, 4) ||
                  misaligned(p.res_post2, 4) || misaligned(p.y, 4));
-  const bool vec_combine =
+  plan.vec_combine =
       Cout % 8 == 0 &&
       !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
         misaligned(p.res, 16) || misaligned(p.res_post, 16) ||
-        misaligned(p.res_post2, 16) || misaligned(p.y, 16) ||
-        misaligned(p.ws, 16));
+        misaligned(p.res_post2, 16) || misaligned(p.y, 16));
   p.m32 = p.M + BM < (1LL << 31);
-  dim3 grid(ntiles * splitk), block(256);
-  // short-K blocks (the 1x1 layers: <= 6 chunks) never reach pipeline
-  // steady state with single-stage prefetch — use the 2-deep variant there
-  const int nk_block = (nk_total + splitk - 1) / splitk;
-  const bool deep = nk_block <= 6;
+  plan.BM = BM;
+  plan.BN = BN;
+  plan.nblocks = t.ntiles * splitk;
+  plan.nk_block = t.nk_block;
+  plan.deep = t.deep;
+  return plan;
+}
+
+// the workspace pointer completes a plan (its alignment gates vec_combine)
+void set_workspace(ConvPlan& plan, float* ws) {
+  plan.p.ws = ws;
+  plan.vec_combine = plan.vec_combine && !misaligned(ws, 16);
+}
+
+int combine_blocks(const ConvPlan& plan) {
+  const long long total = plan.p.M * plan.p.Cout;
+  return ibp::grid_1d(plan.vec_combine ? total / 8 : total, 256, 4096);
+}
+
+void launch_single(const ConvPlan& plan, hipStream_t stream) {
+  const ibp::ConvParams& p = plan.p;
+  dim3 grid(plan.nblocks), block(256);
+  const int BM = plan.BM, BN = plan.BN;
+  const bool deep = plan.deep;
   if (BM == 128 && BN == 128) {
     if (deep)
       hipLaunchKernelGGL((ibp::conv_mfma_kernel<128, 128, true>), grid, block, 0, stream, p);
@@ -805,22 +1017,164 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
     else
       hipLaunchKernelGGL((ibp::conv_mfma_kernel<32, 64>), grid, block, 0, stream, p);
   }
-  if (splitk > 1) {
-    long long total = (long long)p.M * Cout;
-    dim3 cblock(256);
-    if (vec_combine) {
-      dim3 cgrid(ibp::grid_1d(total / 8, 256, 4096));
+  if (p.splitk > 1) {
+    long long total = (long long)p.M * p.Cout;
+    dim3 cblock(256), cgrid(combine_blocks(plan));
+    if (plan.vec_combine) {
       hipLaunchKernelGGL(ibp::splitk_combine_kernel<true>, cgrid, cblock, 0,
                          stream, p.ws, p.y, p.scale, p.shift, p.res,
-                         p.res_post, p.res_post2, total, (int)Cout, p.act,
-                         splitk);
+                         p.res_post, p.res_post2, total, p.Cout, p.act,
+                         p.splitk);
     } else {
-      dim3 cgrid(ibp::grid_1d(total, 256, 4096));
       hipLaunchKernelGGL(ibp::splitk_combine_kernel<false>, cgrid, cblock, 0,
                          stream, p.ws, p.y, p.scale, p.shift, p.res,
-                         p.res_post, p.res_post2, total, (int)Cout, p.act,
-                         splitk);
+                         p.res_post, p.res_post2, total, p.Cout, p.act,
+                         p.splitk);
     }
   }
-  return y;
+}
+
+// one grouped conv launch (+ one grouped combine) over plans[first, last)
+void launch_group(std::vector<ConvPlan>& plans, size_t first, size_t last,
+                  const at::TensorOptions& f32, hipStream_t stream,
+                  std::vector<Tensor>& keep) {
+  const int n = (int)(last - first);
+  // one workspace for all split members, 16-byte-aligned sub-allocations
+  long long ws_total = 0;
+  std::vector<long long> ws_off(n, 0);
+  for (int i = 0; i < n; ++i) {
+    ws_off[i] = ws_total;
+    ws_total += (plans[first + i].ws_elems + 3) / 4 * 4;
+  }
+  if (ws_total > 0) {
+    Tensor ws = torch::empty({ws_total}, f32);
+    keep.push_back(ws);
+    for (int i = 0; i < n; ++i)
+      if (plans[first + i].ws_elems > 0)
+        set_workspace(plans[first + i], ws.data_ptr<float>() + ws_off[i]);
+  }
+  // blocks with the most K-chunks first; ties keep list order (deterministic)
+  std::vector<int> order(n);
+  for (int i = 0; i < n; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return plans[first + a].nk_block > plans[first + b].nk_block;
+  });
+  ibp::ConvGroupParams g{};
+  ibp::CombineGroupParams cg{};
+  int blocks = 0, cblocks = 0, nc = 0;
+  for (int i = 0; i < ibp::kMaxGroup; ++i) {
+    const ConvPlan& plan = plans[first + order[i < n ? i : n - 1]];
+    if (i < n) blocks += plan.nblocks;
+    g.p[i] = plan.p;
+    g.cfg[i] = ibp::tile_cfg(plan.BM, plan.BN, plan.deep);
+    g.block_end[i] = blocks;
+  }
+  g.n = n;
+  for (int i = 0; i < n; ++i) {
+    const ConvPlan& plan = plans[first + order[i]];
+    if (plan.p.splitk <= 1) continue;
+    const ibp::ConvParams& p = plan.p;
+    cblocks += combine_blocks(plan);
+    cg.c[nc] = ibp::CombineProblem{p.ws, p.y, p.scale, p.shift, p.res,
+                                   p.res_post, p.res_post2,
+                                   (long long)p.M * p.Cout, p.Cout, p.act,
+                                   p.splitk, plan.vec_combine ? 1 : 0};
+    cg.block_end[nc] = cblocks;
+    ++nc;
+  }
+  for (int i = nc; i < ibp::kMaxGroup; ++i) {
+    cg.c[i] = cg.c[nc > 0 ? nc - 1 : 0];
+    cg.block_end[i] = cblocks;
+  }
+  cg.n = nc;
+  hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel, dim3(blocks), dim3(256), 0,
+                     stream, g);
+  if (nc > 0)
+    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel, dim3(cblocks),
+                       dim3(256), 0, stream, cg);
+}
+
+}  // namespace
+
+Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
+                     int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                     int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
+                     int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
+                     int64_t Wo, const c10::optional<Tensor>& scale,
+                     const c10::optional<Tensor>& shift,
+                     const c10::optional<Tensor>& residual, bool act,
+                     const c10::optional<Tensor>& residual_post,
+                     const c10::optional<Tensor>& residual_post2, int64_t zs) {
+  ConvPlan plan = plan_conv(x, w_packed, N, H, W, Cin, Cout, KH, KW, stride,
+                            pad_h, pad_w, dil_h, dil_w, Ho, Wo, scale, shift,
+                            residual, act, residual_post, residual_post2, zs);
+  Tensor ws;
+  if (plan.ws_elems > 0) {
+    ws = torch::empty({plan.ws_elems}, x.options().dtype(torch::kFloat32));
+    set_workspace(plan, ws.data_ptr<float>());
+  }
+  launch_single(plan, at::hip::getCurrentHIPStream().stream());
+  return plan.y;
+}
+
+// Several independent convs in as few launches as possible: lists of the
+// conv_mfma_fwd arguments (geom[i] = {N, H, W, Cin, Cout, KH, KW, stride,
+// pad_h, pad_w, dil_h, dil_w, Ho, Wo, zs}), outputs in list order. Every
+// member keeps the plan it gets alone — same tile, split, epilogue path and
+// summation order — so each output is bit-identical to the single call.
+std::vector<Tensor> conv_mfma_fwd_grouped(
+    const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
+    const std::vector<std::vector<int64_t>>& geom,
+    const std::vector<c10::optional<Tensor>>& scales,
+    const std::vector<c10::optional<Tensor>>& shifts,
+    const std::vector<c10::optional<Tensor>>& residuals,
+    const std::vector<int64_t>& acts,
+    const std::vector<c10::optional<Tensor>>& residual_posts,
+    const std::vector<c10::optional<Tensor>>& residual_post2s) {
+  const size_t n = xs.size();
+  TORCH_CHECK(n > 0 && ws_packed.size() == n && geom.size() == n &&
+              scales.size() == n && shifts.size() == n &&
+              residuals.size() == n && acts.size() == n &&
+              residual_posts.size() == n && residual_post2s.size() == n,
+              "conv_mfma_fwd_grouped: argument lists differ in length");
+  std::vector<ConvPlan> plans;
+  plans.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    const auto& q = geom[i];
+    TORCH_CHECK(q.size() == 15, "conv_mfma_fwd_grouped: geom needs 15 ints");
+    TORCH_CHECK(xs[i].device() == xs[0].device());
+    plans.push_back(plan_conv(xs[i], ws_packed[i], q[0], q[1], q[2], q[3],
+                              q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11],
+                              q[12], q[13], scales[i], shifts[i], residuals[i],
+                              acts[i] != 0, residual_posts[i],
+                              residual_post2s[i], q[14]));
+  }
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  const auto f32 = xs[0].options().dtype(torch::kFloat32);
+  std::vector<Tensor> keep;
+  for (size_t first = 0; first < n; first += ibp::kMaxGroup) {
+    const size_t last = std::min(n, first + (size_t)ibp::kMaxGroup);
+    if (last - first == 1) {
+      ConvPlan& plan = plans[first];
+      if (plan.ws_elems > 0) {
+        keep.push_back(torch::empty({plan.ws_elems}, f32));
+        set_workspace(plan, keep.back().data_ptr<float>());
+      }
+      launch_single(plan, stream);
+    } else {
+      launch_group(plans, first, last, f32, stream, keep);
+    }
+  }
+  std::vector<Tensor> ys;
+  ys.reserve(n);
+  for (auto& plan : plans) ys.push_back(plan.y);
+  return ys;
+}
+
+// {BM, BN, splitk, deep} that a conv with these GEMM extents is planned with
+// (M = N*Ho*Wo, K = KH*KW*Cin) — lets tests assert which tile and split a
+// shape lands on.
+std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K) {
+  const TilePlan t = plan_tile(M, (int)Cout, (int)K);
+  return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
 }

@@ -109,33 +109,41 @@ __global__ void upsample2x_bwd_kernel(const T* __restrict__ dy, T* __restrict__ 
 // Partials go to a [N][rows][C] workspace with plain stores; a column-sum
 // stage reduces rows (the previous atomicAdd form serialised rows-way per
 // (n,c) address and needed a zero-init launch).
+// (bx, by, n) / rows are the block coordinates and the x-extent of the
+// problem's own grid — the grouped launch below passes problem-local ones.
 template <typename T, bool PROD>
-__global__ void se_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b,
-                                 float* __restrict__ ws, int N, long long HW, int C) {
-  int c = blockIdx.y * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void se_reduce_body(
+    const T* __restrict__ a, const T* __restrict__ b, float* __restrict__ ws,
+    long long HW, int C, int bx, int by, int n, int rows) {
+  int c = by * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  int n = blockIdx.z;
   const T* pa = a + (long long)n * HW * C;
   const T* pb = PROD ? b + (long long)n * HW * C : nullptr;
   float s = 0.f;
-  for (long long m = blockIdx.x; m < HW; m += gridDim.x) {
+  for (long long m = bx; m < HW; m += rows) {
     float v = ldf(pa + m * C + c);
     if (PROD) v *= ldf(pb + m * C + c);
     s += v;
   }
-  ws[((long long)n * gridDim.x + blockIdx.x) * C + c] = s;
+  ws[((long long)n * rows + bx) * C + c] = s;
+}
+
+template <typename T, bool PROD>
+__global__ void se_reduce_kernel(const T* __restrict__ a, const T* __restrict__ b,
+                                 float* __restrict__ ws, int N, long long HW, int C) {
+  se_reduce_body<T, PROD>(a, b, ws, HW, C, blockIdx.x, blockIdx.y, blockIdx.z,
+                          gridDim.x);
 }
 
 // out[p][c] = sum_r ws[p][r][c] (same shape as bn_act.hip's colsum; kept
 // local — device code cannot cross TUs under -fno-gpu-rdc)
-__global__ __launch_bounds__(1024) void se_colsum_kernel(
+__device__ __forceinline__ void se_colsum_body(
     const float* __restrict__ ws, float* __restrict__ out, int rows, int C,
-    int planes) {
-  __shared__ float red[1024];
+    int planes, int bid, float* red) {
   const int total = C * planes;
   const int cl = threadIdx.x & 63;
   const int rl = threadIdx.x >> 6;
-  const int i = blockIdx.x * 64 + cl;
+  const int i = bid * 64 + cl;
   float a = 0.f;
   if (i < total) {
     const int p = i / C;
@@ -152,19 +160,24 @@ __global__ __launch_bounds__(1024) void se_colsum_kernel(
   }
 }
 
+__global__ __launch_bounds__(1024) void se_colsum_kernel(
+    const float* __restrict__ ws, float* __restrict__ out, int rows, int C,
+    int planes) {
+  __shared__ float red[1024];
+  se_colsum_body(ws, out, rows, C, planes, blockIdx.x, red);
+}
+
 // y = x * s[n][c] (+ optional add[n][c] broadcast)
 
 // fused SE gate: s = sigmoid(W2 @ leaky(W1 @ pooled + b1) + b2) — replaces
 // two library GEMM launches + bias/activation elementwise on the inference
 // path (the FCs are 256x16: far below any GEMM library's useful size).
 template <typename T>
-__global__ void se_gate_kernel(const float* __restrict__ pooled,
-                               const T* __restrict__ w1, const T* __restrict__ b1,
-                               const T* __restrict__ w2, const T* __restrict__ b2,
-                               float* __restrict__ s, int C, int CH,
-                               float slope, float pool_scale) {
-  __shared__ float pl[768 + 64];
-  const int n = blockIdx.x;
+__device__ __forceinline__ void se_gate_body(
+    const float* __restrict__ pooled, const T* __restrict__ w1,
+    const T* __restrict__ b1, const T* __restrict__ w2,
+    const T* __restrict__ b2, float* __restrict__ s, int C, int CH,
+    float slope, float pool_scale, int n, float* pl) {
   const int tid = threadIdx.x;
   // pool_scale folds the GAP division (sums -> mean) into this kernel
   for (int c = tid; c < C; c += blockDim.x)
@@ -183,6 +196,17 @@ __global__ void se_gate_kernel(const float* __restrict__ pooled,
     for (int j = 0; j < CH; ++j) acc += ldf(row + j) * pl[C + j];
     s[(long long)n * C + c] = 1.f / (1.f + __expf(-acc));
   }
+}
+
+template <typename T>
+__global__ void se_gate_kernel(const float* __restrict__ pooled,
+                               const T* __restrict__ w1, const T* __restrict__ b1,
+                               const T* __restrict__ w2, const T* __restrict__ b2,
+                               float* __restrict__ s, int C, int CH,
+                               float slope, float pool_scale) {
+  __shared__ float pl[768 + 64];
+  se_gate_body<T>(pooled, w1, b1, w2, b2, s, C, CH, slope, pool_scale,
+                  blockIdx.x, pl);
 }
 
 template <typename T>
@@ -314,14 +338,13 @@ __global__ void upsample2x_bwd_bf16v8(const ushort8v* __restrict__ dy,
   }
 }
 
-__global__ void se_scale_bf16v8(const ushort8v* __restrict__ x,
-                                const float* __restrict__ s,
-                                const float* __restrict__ addc,
-                                ushort8v* __restrict__ y,
-                                int N, long long HW, int C8) {
+__device__ __forceinline__ void se_scale_bf16v8_body(
+    const ushort8v* __restrict__ x, const float* __restrict__ s,
+    const float* __restrict__ addc, ushort8v* __restrict__ y, int N,
+    long long HW, int C8, int bid, int nblocks) {
   const long long total = (long long)N * HW * C8;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-       i < total; i += (long long)gridDim.x * blockDim.x) {
+  for (long long i = bid * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)nblocks * blockDim.x) {
     const int c8 = (int)(i % C8);
     const int n = (int)(i / (HW * C8));
     const float* sc = s + (long long)n * C8 * 8 + c8 * 8;
@@ -336,6 +359,93 @@ __global__ void se_scale_bf16v8(const ushort8v* __restrict__ x,
     }
     y[i] = out;
   }
+}
+
+__global__ void se_scale_bf16v8(const ushort8v* __restrict__ x,
+                                const float* __restrict__ s,
+                                const float* __restrict__ addc,
+                                ushort8v* __restrict__ y,
+                                int N, long long HW, int C8) {
+  se_scale_bf16v8_body(x, s, addc, y, N, HW, C8, blockIdx.x, gridDim.x);
+}
+
+// ---- grouped squeeze-excitation (inference): the SE layers of several
+// independent feature maps (the five scales of one stack) in ONE launch per
+// stage. Same block -> problem table scheme as the grouped conv: end[i] is
+// the exclusive prefix sum of the problems' block counts for the stage being
+// launched; each problem runs the single kernels' bodies with its own local
+// grid, so the arithmetic and every reduction order are those of the single
+// calls. bf16 feature maps and parameters only.
+constexpr int kSeMaxGroup = 8;
+
+struct SeProblem {
+  const c10::BFloat16* x;
+  c10::BFloat16* y;
+  float* ws;        // [N][rows][C] GAP partials
+  float* pooled;    // [N][C] GAP sums
+  float* s;         // [N][C] gate
+  const c10::BFloat16 *w1, *b1, *w2, *b2;
+  long long HW;
+  int N, C, CH, rows, cy;
+  float pool_scale;
+};
+
+struct SeGroupParams {
+  SeProblem q[kSeMaxGroup];
+  int end[kSeMaxGroup];
+  int n;
+  float slope;
+};
+
+// copy of the block's problem out of the kernel arguments + local block id
+__device__ __forceinline__ SeProblem se_find(const SeGroupParams& g, int& bid,
+                                             int& nblocks) {
+  SeProblem q = g.q[0];
+  int base = 0, end = g.end[0];
+  #pragma unroll
+  for (int i = 0; i < kSeMaxGroup - 1; ++i) {
+    if (i + 1 < g.n && bid >= g.end[i]) {
+      q = g.q[i + 1];
+      base = g.end[i];
+      end = g.end[i + 1];
+    }
+  }
+  nblocks = end - base;
+  bid -= base;
+  return q;
+}
+
+__global__ void se_reduce_grouped_kernel(SeGroupParams g) {
+  int bid = blockIdx.x, nblocks;
+  const SeProblem q = se_find(g, bid, nblocks);
+  const int bx = bid % q.rows;
+  const int t = bid / q.rows;
+  se_reduce_body<c10::BFloat16, false>(q.x, nullptr, q.ws, q.HW, q.C, bx,
+                                        t % q.cy, t / q.cy, q.rows);
+}
+
+__global__ __launch_bounds__(1024) void se_colsum_grouped_kernel(
+    SeGroupParams g) {
+  __shared__ float red[1024];
+  int bid = blockIdx.x, nblocks;
+  const SeProblem q = se_find(g, bid, nblocks);
+  se_colsum_body(q.ws, q.pooled, q.rows, q.C, q.N, bid, red);
+}
+
+__global__ void se_gate_grouped_kernel(SeGroupParams g) {
+  __shared__ float pl[768 + 64];
+  int bid = blockIdx.x, nblocks;
+  const SeProblem q = se_find(g, bid, nblocks);
+  se_gate_body<c10::BFloat16>(q.pooled, q.w1, q.b1, q.w2, q.b2, q.s, q.C,
+                               q.CH, g.slope, q.pool_scale, bid, pl);
+}
+
+__global__ void se_scale_grouped_kernel(SeGroupParams g) {
+  int bid = blockIdx.x, nblocks;
+  const SeProblem q = se_find(g, bid, nblocks);
+  se_scale_bf16v8_body(reinterpret_cast<const ushort8v*>(q.x), q.s, nullptr,
+                       reinterpret_cast<ushort8v*>(q.y), q.N, q.HW, q.C / 8,
+                       bid, nblocks);
 }
 
 }  // namespace ibp
@@ -532,4 +642,101 @@ Tensor se_scale(const Tensor& x, const Tensor& s, const c10::optional<Tensor>& a
                        reinterpret_cast<T*>(y.data_ptr()), (int)N, HW, (int)C);
   });
   return y;
+}
+
+// Inference SE layers of up to kSeMaxGroup-sized chunks of independent
+// feature maps: se_reduce + colsum + gate + scale, ONE launch each per chunk
+// instead of one per map. xs[i] is NHWC bf16 [N, H, W, C] storage seen as
+// NCHW channels_last; returns the scaled maps in order.
+std::vector<Tensor> se_layer_grouped(const std::vector<Tensor>& xs,
+                                     const std::vector<Tensor>& w1s,
+                                     const std::vector<Tensor>& b1s,
+                                     const std::vector<Tensor>& w2s,
+                                     const std::vector<Tensor>& b2s,
+                                     double slope) {
+  const size_t n = xs.size();
+  TORCH_CHECK(n > 0 && w1s.size() == n && b1s.size() == n &&
+              w2s.size() == n && b2s.size() == n,
+              "se_layer_grouped: argument lists differ in length");
+  const auto bf16 = at::ScalarType::BFloat16;
+  std::vector<Tensor> ys;
+  ys.reserve(n);
+  const auto f32 = xs[0].options().dtype(torch::kFloat32);
+  for (size_t first = 0; first < n; first += ibp::kSeMaxGroup) {
+    const int m = (int)std::min(n - first, (size_t)ibp::kSeMaxGroup);
+    ibp::SeGroupParams g{};
+    g.n = m;
+    g.slope = (float)slope;
+    // one fp32 scratch allocation per chunk: partials, sums and gates
+    std::vector<long long> off(m);
+    long long scratch = 0;
+    for (int i = 0; i < m; ++i) {
+      const Tensor& x = xs[first + i];
+      const Tensor& w1 = w1s[first + i];
+      const Tensor& w2 = w2s[first + i];
+      const Tensor& b1 = b1s[first + i];
+      const Tensor& b2 = b2s[first + i];
+      TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == bf16 &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+                  "se_layer_grouped: x must be bf16 channels_last");
+      const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+      const int64_t CH = w1.size(0);
+      TORCH_CHECK(C % 8 == 0 && C <= 768 && CH <= 64,
+                  "se_layer_grouped: C % 8 == 0, C <= 768, CH <= 64");
+      TORCH_CHECK(w1.scalar_type() == bf16 && b1.scalar_type() == bf16 &&
+                  w2.scalar_type() == bf16 && b2.scalar_type() == bf16 &&
+                  w1.is_contiguous() && w2.is_contiguous() &&
+                  b1.is_contiguous() && b2.is_contiguous(),
+                  "se_layer_grouped: bf16 contiguous FC parameters");
+      TORCH_CHECK(w1.dim() == 2 && w1.size(1) == C && b1.numel() == CH &&
+                  w2.dim() == 2 && w2.size(0) == C && w2.size(1) == CH &&
+                  b2.numel() == C,
+                  "se_layer_grouped: expected w1 [CH,C], b1 [CH], w2 [C,CH], b2 [C]");
+      ibp::SeProblem& q = g.q[i];
+      q.N = (int)N; q.C = (int)C; q.CH = (int)CH; q.HW = HW;
+      q.rows = (int)std::min<long long>((HW + 63) / 64, 512);
+      q.cy = (int)((C + 255) / 256);
+      q.pool_scale = (float)(1.0 / (double)HW);
+      off[i] = scratch;
+      scratch += (N * q.rows * C + 2 * N * C + 3) / 4 * 4;
+    }
+    Tensor buf = torch::empty({scratch}, f32);
+    int e_reduce[ibp::kSeMaxGroup], e_colsum[ibp::kSeMaxGroup];
+    int e_gate[ibp::kSeMaxGroup], e_scale[ibp::kSeMaxGroup];
+    int nr = 0, nc = 0, ng = 0, ns = 0;
+    for (int i = 0; i < ibp::kSeMaxGroup; ++i) {
+      if (i < m) {
+        const Tensor& x = xs[first + i];
+        ibp::SeProblem& q = g.q[i];
+        Tensor y = torch::empty_like(x);
+        ys.push_back(y);
+        q.x = reinterpret_cast<const c10::BFloat16*>(x.data_ptr());
+        q.y = reinterpret_cast<c10::BFloat16*>(y.data_ptr());
+        q.ws = buf.data_ptr<float>() + off[i];
+        q.pooled = q.ws + (long long)q.N * q.rows * q.C;
+        q.s = q.pooled + (long long)q.N * q.C;
+        q.w1 = reinterpret_cast<const c10::BFloat16*>(w1s[first + i].data_ptr());
+        q.b1 = reinterpret_cast<const c10::BFloat16*>(b1s[first + i].data_ptr());
+        q.w2 = reinterpret_cast<const c10::BFloat16*>(w2s[first + i].data_ptr());
+        q.b2 = reinterpret_cast<const c10::BFloat16*>(b2s[first + i].data_ptr());
+        nr += q.rows * q.cy * q.N;
+        nc += (q.N * q.C + 63) / 64;
+        ng += q.N;
+        ns += ibp::grid_1d(x.numel() / 8, 256, 8192);
+      } else {
+        g.q[i] = g.q[m - 1];
+      }
+      e_reduce[i] = nr; e_colsum[i] = nc; e_gate[i] = ng; e_scale[i] = ns;
+    }
+    auto stream = cur_stream2();
+    auto launch = [&](auto kernel, const int* ends, int blocks, int threads) {
+      for (int i = 0; i < ibp::kSeMaxGroup; ++i) g.end[i] = ends[i];
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream, g);
+    };
+    launch(ibp::se_reduce_grouped_kernel, e_reduce, nr, 256);
+    launch(ibp::se_colsum_grouped_kernel, e_colsum, nc, 1024);
+    launch(ibp::se_gate_grouped_kernel, e_gate, ng, 256);
+    launch(ibp::se_scale_grouped_kernel, e_scale, ns, 256);
+  }
+  return ys;
 }

@@ -109,6 +109,40 @@ class _SeScaleFn(torch.autograd.Function):
         return dx, ds.to(ctx.sdtype)
 
 
+def se_group_enabled() -> bool:
+    """``IBP_SE_GROUP=0`` (read at call time) restores one SE launch chain per
+    map for A/B runs; ``IBP_CONV_GROUP=0`` switches every grouping off."""
+    import os
+    return os.environ.get("IBP_SE_GROUP", "1") != "0" \
+        and os.environ.get("IBP_CONV_GROUP", "1") != "0"
+
+
+def se_layer_group_hip(items):
+    """SE layers of independent maps — ``items`` is a list of
+    ``(x, fc1, fc2)`` — as four grouped launches (reduce, column sum, gate,
+    scale) instead of four per map. Inference only (grad disabled, bf16 maps
+    and parameters, C % 8 == 0); anything else runs :func:`se_layer_hip` per
+    member. The grouped kernels run the single kernels' bodies per problem,
+    so outputs are bit-identical."""
+    ok = len(items) > 1 and se_group_enabled() and not torch.is_grad_enabled()
+    if ok:
+        bf16 = torch.bfloat16
+        for x, fc1, fc2 in items:
+            c = x.shape[1]
+            if x.dtype != bf16 or c % 8 or c > 768 or fc1.weight.shape[0] > 64 \
+                    or any(t.dtype != bf16 or not t.is_contiguous() for t in
+                           (fc1.weight, fc1.bias, fc2.weight, fc2.bias)):
+                ok = False
+                break
+    if not ok:
+        return [se_layer_hip(x, fc1, fc2) for x, fc1, fc2 in items]
+    return hip_extension().se_layer_grouped(
+        [x.contiguous(memory_format=_CL) for x, _, _ in items],
+        [fc1.weight for _, fc1, _ in items], [fc1.bias for _, fc1, _ in items],
+        [fc2.weight for _, _, fc2 in items], [fc2.bias for _, _, fc2 in items],
+        LEAKY_SLOPE)
+
+
 def se_layer_hip(x, fc1, fc2):
     if not torch.is_grad_enabled():
         # inference: GAP + one fused gate kernel + scale (3 launches instead
