@@ -35,6 +35,7 @@ import torch.nn.functional as F
 
 from ..config import CanonicalConfig, InferenceParams
 from ..ops._backend import use_hip_for, hip_extension
+from ..ops.ensemble import ensemble_merge
 from ..utils import keypoint_heatmap_nms, refine_centroid
 
 
@@ -204,7 +205,11 @@ def find_peaks(heatmap_avg, params, config: CanonicalConfig, max_peaks=512):
                 xr, yr, sc = refine_centroid(heat_np[c], (int(x), int(y)), radius)
                 rows.append((c, xr, yr, sc, heat_np[c, y, x]))
         rows = np.asarray(rows, dtype=np.float32).reshape(-1, 5)
+    return _rows_to_peaks(rows, n_parts)
 
+
+def _rows_to_peaks(rows, n_parts):
+    """(c, x, y, score, peak) rows in (c, y, x) order -> ``all_peaks``."""
     all_peaks = [[] for _ in range(n_parts)]
     for gid, row in enumerate(rows):
         c = int(row[0])
@@ -230,22 +235,8 @@ def _limb_scores_host(paf_np, pa, pb, mid_num, thre2):
     return mean, float((v > thre2).mean()), float(norm)
 
 
-def find_connections(all_peaks, paf_avg, image_height, params, config: CanonicalConfig):
-    """Score + greedily match candidate limbs (reference evaluate.py:206-276).
-
-    ``paf_avg``: (H, W, paf_layers) torch tensor (device or CPU). Scoring of
-    every (limb_type, peakA, peakB) triple is one batched HIP kernel launch;
-    the greedy 1-1 matching per limb type stays on the host.
-
-    Returns ``(connection_all, special_k)`` in the reference's format:
-    per limb type either an (n, 6) array ``[idA, idB, score, i, j, length]``
-    or an empty list.
-    """
-    mid_num = int(params["mid_num"])
-    thre2 = float(params["thre2"])
-    connect_ration = float(params["connect_ration"])
-
-    limbs = config.limbs_conn
+def _candidate_triples(all_peaks, limbs):
+    """Every (limb, peakA id, peakB id) candidate and its (limb, i, j) position."""
     cand_triples = []
     pair_meta = []  # (k, i, j)
     for k, (a_part, b_part) in enumerate(limbs):
@@ -253,27 +244,15 @@ def find_connections(all_peaks, paf_avg, image_height, params, config: Canonical
             for j, pb in enumerate(all_peaks[b_part]):
                 cand_triples.append((k, pa[3], pb[3]))
                 pair_meta.append((k, i, j))
+    return cand_triples, pair_meta
 
-    flat_peaks = [p for sub in all_peaks for p in sub]
-    flat_peaks.sort(key=lambda p: p[3])
 
-    scores = np.zeros((0, 3), dtype=np.float32)
-    if cand_triples:
-        paf = paf_avg.permute(2, 0, 1).contiguous().float()
-        if use_hip_for(paf):
-            ext = hip_extension()
-            peaks_dev = torch.tensor([[0.0, p[0], p[1], p[2], 0.0] for p in flat_peaks],
-                                     dtype=torch.float32, device=paf.device)
-            cand_dev = torch.tensor(cand_triples, dtype=torch.int32, device=paf.device)
-            scores = ext.limb_scores(paf, peaks_dev, cand_dev, mid_num, thre2) \
-                .cpu().numpy()
-        else:
-            paf_np = paf.cpu().numpy()
-            scores = np.array([
-                _limb_scores_host(paf_np[k], flat_peaks[ia], flat_peaks[ib],
-                                  mid_num, thre2)
-                for (k, ia, ib) in cand_triples], dtype=np.float32)
-
+def _greedy_match(all_peaks, scores, pair_meta, params, config: CanonicalConfig):
+    """Greedy 1-1 matching per limb type over scored candidates (the host half
+    of ``find_connections``). ``scores[i]`` = (prior score, pass ratio, length)
+    of candidate ``pair_meta[i]`` = (limb, i, j), grouped by limb in order."""
+    connect_ration = float(params["connect_ration"])
+    limbs = config.limbs_conn
     connection_all, special_k = [], []
     ptr = 0
     counts = {}
@@ -317,6 +296,45 @@ def find_connections(all_peaks, paf_avg, image_height, params, config: Canonical
                 break
         connection_all.append(np.asarray(conn, dtype=np.float64).reshape(-1, 6))
     return connection_all, special_k
+
+
+def find_connections(all_peaks, paf_avg, image_height, params, config: CanonicalConfig):
+    """Score + greedily match candidate limbs (reference evaluate.py:206-276).
+
+    ``paf_avg``: (H, W, paf_layers) torch tensor (device or CPU). Scoring of
+    every (limb_type, peakA, peakB) triple is one batched HIP kernel launch;
+    the greedy 1-1 matching per limb type stays on the host.
+
+    Returns ``(connection_all, special_k)`` in the reference's format:
+    per limb type either an (n, 6) array ``[idA, idB, score, i, j, length]``
+    or an empty list.
+    """
+    mid_num = int(params["mid_num"])
+    thre2 = float(params["thre2"])
+
+    cand_triples, pair_meta = _candidate_triples(all_peaks, config.limbs_conn)
+
+    flat_peaks = [p for sub in all_peaks for p in sub]
+    flat_peaks.sort(key=lambda p: p[3])
+
+    scores = np.zeros((0, 3), dtype=np.float32)
+    if cand_triples:
+        paf = paf_avg.permute(2, 0, 1).contiguous().float()
+        if use_hip_for(paf):
+            ext = hip_extension()
+            peaks_dev = torch.tensor([[0.0, p[0], p[1], p[2], 0.0] for p in flat_peaks],
+                                     dtype=torch.float32, device=paf.device)
+            cand_dev = torch.tensor(cand_triples, dtype=torch.int32, device=paf.device)
+            scores = ext.limb_scores(paf, peaks_dev, cand_dev, mid_num, thre2) \
+                .cpu().numpy()
+        else:
+            paf_np = paf.cpu().numpy()
+            scores = np.array([
+                _limb_scores_host(paf_np[k], flat_peaks[ia], flat_peaks[ib],
+                                  mid_num, thre2)
+                for (k, ia, ib) in cand_triples], dtype=np.float32)
+
+    return _greedy_match(all_peaks, scores, pair_meta, params, config)
 
 
 # --------------------------------------------------------------------------
@@ -490,6 +508,225 @@ def process(image, model, config: CanonicalConfig, params=None, model_params=Non
     subset, candidate = find_people(connection_all, special_k, all_peaks,
                                     params, config)
     return subsets_to_keypoints(subset, candidate, config)
+
+
+# --------------------------------------------------------------------------
+# batched inference: many images per forward, fused ensemble merge, one
+# device->host transfer per post-processing stage
+# --------------------------------------------------------------------------
+
+def _rotate_nchw(x, angle_deg, inverse=False):
+    """``_rotate_hwc`` for an (N, C, H, W) batch."""
+    if angle_deg == 0:
+        return x
+    a = math.radians(angle_deg if not inverse else -angle_deg)
+    cos, sin = math.cos(a), math.sin(a)
+    H, W = x.shape[2], x.shape[3]
+    theta = torch.tensor([[cos, -sin * H / W, 0.0],
+                          [sin * W / H, cos, 0.0]],
+                         dtype=torch.float32, device=x.device)
+    xf = x.float()
+    grid = F.affine_grid(theta[None].expand(x.shape[0], -1, -1), xf.shape,
+                         align_corners=False)
+    out = F.grid_sample(xf, grid, mode="bilinear", padding_mode="zeros",
+                        align_corners=False)
+    return out.to(x.dtype)
+
+
+def _output_channels(config: CanonicalConfig):
+    """``(chan_order, flip_perm)``: where the ``[heat | paf]`` output channels
+    sit in the network's ``[paf | heat]`` output, and the L/R permutation of the
+    mirrored view in that output order."""
+    n_heat = config.num_layers - config.paf_layers
+    n_paf = config.paf_layers
+    chan_order = list(range(n_paf, n_paf + n_heat)) + list(range(n_paf))
+    flip_perm = [int(c) for c in config.flip_heat_ord] + \
+        [n_heat + int(c) for c in config.flip_paf_ord]
+    return chan_order, flip_perm
+
+
+@torch.no_grad()
+def _predict_groups(images, model, config, params, model_params, max_views,
+                    device=None, dtype=None):
+    """Ensemble forward of a list of images. Returns ``[(indices, maps)]``, one
+    entry per distinct image size: ``maps`` is the planar fp32
+    (n, heat + paf, H, W) average of the images ``indices`` in that order."""
+    if params is None or model_params is None:
+        p, mp = InferenceParams().as_params_dict()
+        params = params or p
+        model_params = model_params or mp
+    if device is None:
+        device = next(model.parameters()).device
+    if dtype is None:
+        dtype = next(model.parameters()).dtype
+    if max_views < 2:
+        raise ValueError("max_views must allow an image and its mirror (>= 2)")
+    chunk = max_views // 2
+
+    chan_order, flip_perm = _output_channels(config)
+    rotations = params.get("rotation_search", [0.0])
+    pad_to = model_params["max_downsample"]
+    pad_value = model_params["padValue"] / 255.0
+
+    by_size = {}
+    for i, image in enumerate(images):
+        img = _to_device_image(image, device)
+        by_size.setdefault((img.shape[0], img.shape[1]), []).append((i, img))
+
+    groups = []
+    for (H, W), members in by_size.items():
+        idxs = [i for i, _ in members]
+        imgs = torch.stack([t for _, t in members]).permute(0, 3, 1, 2)  # NCHW
+        n = len(idxs)
+        maps = torch.empty(n, len(chan_order), H, W, device=device,
+                           dtype=torch.float32)
+        multiplier = [s * model_params["boxsize"] / H
+                      for s in params["scale_search"]]
+        n_runs = len(multiplier) * len(rotations)
+        first = True
+        for scale in multiplier:
+            # cap absurdly large upscales (reference evaluate.py:94-96)
+            if scale * H > 2600 or scale * W > 3800:
+                scale = min(2600 / H, 3800 / W)
+            sh, sw = max(int(round(H * scale)), 1), max(int(round(W * scale)), 1)
+            scaled = F.interpolate(imgs, size=(sh, sw), mode="bicubic",
+                                   align_corners=False)
+            pad_h = (pad_to - sh % pad_to) % pad_to
+            pad_w = (pad_to - sw % pad_to) % pad_to
+            padded0 = F.pad(scaled, (0, pad_w, 0, pad_h), value=pad_value)
+            ph, pw = padded0.shape[2], padded0.shape[3]
+            for angle in rotations:
+                padded = _rotate_nchw(padded0, angle)
+                flipped = torch.flip(padded, dims=[3])
+                for lo in range(0, n, chunk):
+                    hi = min(lo + chunk, n)
+                    batch = torch.cat([padded[lo:hi], flipped[lo:hi]]) \
+                        .permute(0, 2, 3, 1).contiguous().to(dtype)   # NHWC
+                    out = model(batch)[-1][0]            # last stack, scale 0
+                    stride = ph // out.shape[2]
+                    assert out.shape[2] * stride == ph and \
+                        out.shape[3] * stride == pw, "non-integer output stride"
+                    if angle == 0:
+                        ensemble_merge(out, flip_perm, stride, (sh, sw), (H, W),
+                                       scale=1.0 / n_runs, out=maps[lo:hi],
+                                       accumulate=not first,
+                                       chan_order=chan_order)
+                        continue
+                    # rotated runs keep the torch chain, batched along N
+                    v = out.float()[:, chan_order]
+                    merged = (v[:hi - lo] +
+                              torch.flip(v[hi - lo:], dims=[-1])[:, flip_perm]) * 0.5
+                    up = F.interpolate(merged, size=(ph, pw), mode="bicubic",
+                                       align_corners=False)
+                    up = _rotate_nchw(up, angle, inverse=True)[:, :, :sh, :sw]
+                    up = F.interpolate(up, size=(H, W), mode="bicubic",
+                                       align_corners=False) / n_runs
+                    if first:
+                        maps[lo:hi] = up
+                    else:
+                        maps[lo:hi] += up
+                first = False
+        groups.append((idxs, maps))
+    return groups
+
+
+def predict_batch(images, model, config: CanonicalConfig, params=None,
+                  model_params=None, max_views=16, device=None, dtype=None):
+    """``predict`` for a list of (H, W, 3) images.
+
+    Images are grouped by size; per scale and rotation each group goes through
+    the model as ``[views | mirrored views]`` in chunks of at most ``max_views``
+    views, and rotation-free runs are merged by the fused ``ensemble_merge``
+    kernel. Returns one ``(heatmap_avg, paf_avg)`` per image in input order,
+    laid out as ``predict`` returns them: (H, W, C) views of a planar buffer.
+    """
+    n_heat = config.num_layers - config.paf_layers
+    results = [None] * len(images)
+    for idxs, maps in _predict_groups(images, model, config, params,
+                                      model_params, max_views, device, dtype):
+        for j, i in enumerate(idxs):
+            results[i] = (maps[j, :n_heat].permute(1, 2, 0),
+                          maps[j, n_heat:].permute(1, 2, 0))
+    return results
+
+
+def find_peaks_batch(maps, params, config: CanonicalConfig, max_peaks=512):
+    """``find_peaks`` over a planar (N, heat + paf, H, W) fp32 buffer: one
+    kernel launch and one device->host copy for the batch. Returns one
+    ``all_peaks`` per image (peak ids are per image, as in ``find_peaks``)."""
+    n_parts = config.heat_layers
+    if not use_hip_for(maps):
+        return [find_peaks(maps[n, :n_parts].permute(1, 2, 0), params, config,
+                           max_peaks) for n in range(maps.shape[0])]
+    buf = hip_extension().peaks_batched(
+        maps.contiguous(), n_parts, float(params["thre1"]),
+        int(params["offset_radius"]), max_peaks).cpu().numpy()
+    counts = np.ascontiguousarray(buf[:, 0, 0]).view(np.int32)
+    out = []
+    for n in range(buf.shape[0]):
+        rows = buf[n, 1:1 + min(int(counts[n]), max_peaks)]
+        # atomics make device order nondeterministic: impose (c, y, x) order
+        rows = rows[np.lexsort((rows[:, 1], rows[:, 2], rows[:, 0]))]
+        out.append(_rows_to_peaks(rows, n_parts))
+    return out
+
+
+def find_connections_batch(all_peaks_list, maps, params, config: CanonicalConfig):
+    """``find_connections`` for every image of a planar (N, heat + paf, H, W)
+    buffer: all images' candidates are scored in one kernel launch with one
+    copy back; the greedy matching runs per image on the host."""
+    n_heat = config.num_layers - config.paf_layers
+    if not use_hip_for(maps):
+        return [find_connections(pk, maps[n, n_heat:].permute(1, 2, 0),
+                                 maps.shape[2], params, config)
+                for n, pk in enumerate(all_peaks_list)]
+    maps = maps.contiguous()
+    planes = maps.shape[1]
+    cands, metas, peak_rows = [], [], []
+    for n, all_peaks in enumerate(all_peaks_list):
+        triples, meta = _candidate_triples(all_peaks, config.limbs_conn)
+        base = len(peak_rows)
+        flat = sorted((p for sub in all_peaks for p in sub), key=lambda p: p[3])
+        peak_rows.extend([0.0, p[0], p[1], p[2], 0.0] for p in flat)
+        # the kernel picks its plane by the first field: this image's limb k
+        cands.extend((n * planes + n_heat + k, base + ia, base + ib)
+                     for k, ia, ib in triples)
+        metas.append(meta)
+    scores = np.zeros((0, 3), dtype=np.float32)
+    if cands:
+        peaks_dev = torch.tensor(peak_rows, dtype=torch.float32, device=maps.device)
+        cand_dev = torch.tensor(cands, dtype=torch.int32, device=maps.device)
+        scores = hip_extension().limb_scores(
+            maps, peaks_dev, cand_dev, int(params["mid_num"]),
+            float(params["thre2"])).cpu().numpy()
+    out, ptr = [], 0
+    for all_peaks, meta in zip(all_peaks_list, metas):
+        out.append(_greedy_match(all_peaks, scores[ptr:ptr + len(meta)], meta,
+                                 params, config))
+        ptr += len(meta)
+    return out
+
+
+@torch.no_grad()
+def process_batch(images, model, config: CanonicalConfig, params=None,
+                  model_params=None, max_views=16):
+    """``process`` for a list of images: batched forward and ensemble merge,
+    batched peak and limb kernels, then the per-image greedy assembly. Returns
+    one ``process`` result per image, in input order."""
+    if params is None or model_params is None:
+        p, mp = InferenceParams().as_params_dict()
+        params = params or p
+        model_params = model_params or mp
+    results = [None] * len(images)
+    for idxs, maps in _predict_groups(images, model, config, params,
+                                      model_params, max_views):
+        peaks = find_peaks_batch(maps, params, config)
+        conns = find_connections_batch(peaks, maps, params, config)
+        for i, all_peaks, (connection_all, special_k) in zip(idxs, peaks, conns):
+            subset, candidate = find_people(connection_all, special_k, all_peaks,
+                                            params, config)
+            results[i] = subsets_to_keypoints(subset, candidate, config)
+    return results
 
 
 def format_results(keypoints, res_file):

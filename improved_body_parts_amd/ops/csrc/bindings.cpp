@@ -106,6 +106,15 @@ std::vector<Tensor> collect_peaks(const Tensor& nmsed, const Tensor& smoothed,
                                   int64_t radius, int64_t max_peaks);
 Tensor limb_scores(const Tensor& paf, const Tensor& peaks, const Tensor& cand_idx,
                    int64_t mid_num, double thre2);
+Tensor peaks_batched(const Tensor& maps, int64_t heat_layers, double thre,
+                     int64_t radius, int64_t max_peaks);
+
+// ensemble_merge.hip
+void ensemble_merge(const Tensor& src, const Tensor& chan_main,
+                    const Tensor& chan_flip, const Tensor& ystart,
+                    const Tensor& yw, const Tensor& xstart, const Tensor& xw,
+                    Tensor& out, double scale, bool accumulate, int64_t cb,
+                    int64_t wr, int64_t wc, int64_t span);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_stats", &bn_stats, "per-channel sum/sumsq of an [M][C] view");
@@ -164,4 +173,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("heatmap_nms", &heatmap_nms);
   m.def("collect_peaks", &collect_peaks);
   m.def("limb_scores", &limb_scores);
+  m.def("peaks_batched", &peaks_batched,
+        "fused NMS + centroid refinement over a planar batch, per-image counters",
+        py::arg("maps"), py::arg("heat_layers"), py::arg("thre"),
+        py::arg("radius"), py::arg("max_peaks"));
+  m.def("ensemble_merge", &ensemble_merge,
+        "flip-merge + composed bicubic resample of the low-res network output",
+        py::arg("src"), py::arg("chan_main"), py::arg("chan_flip"),
+        py::arg("ystart"), py::arg("yw"), py::arg("xstart"), py::arg("xw"),
+        py::arg("out"), py::arg("scale"), py::arg("accumulate"), py::arg("cb"),
+        py::arg("wr"), py::arg("wc"), py::arg("span"));
 }

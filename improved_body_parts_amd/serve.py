@@ -5,6 +5,8 @@ serving on MI355X, so the full device-resident pipeline (predict -> HIP
 peak/limb kernels -> greedy assembly) is exposed behind an HTTP API:
 
     POST /pose    image (PNG/JPEG bytes, .npy array, or JSON) -> people
+    POST /pose_batch  images ((N, H, W, 3) .npy or a JSON list of images)
+                  -> list of /pose payloads, through the batched pipeline
     GET  /healthz liveness + device/native-path report
     GET  /info    model/config summary
 
@@ -14,6 +16,7 @@ Run: ``python scripts/serve.py --checkpoint ckpt.pth [--port 8000]``
 A single model instance is shared; requests serialise on a lock (the GPU
 pipeline is throughput-bound, not latency-bound — batching across requests
 is a deliberate non-goal at this model size: one 512^2 forward is ~3 ms).
+A client that holds several images sends them together to /pose_batch.
 """
 import io
 import threading
@@ -29,7 +32,7 @@ except Exception:  # pragma: no cover
 
 from .config import GetConfig, TrainingOpt
 from .config.inference_params import InferenceParams
-from .engine.inference import process
+from .engine.inference import process, process_batch
 from .models import NetworkEval
 
 
@@ -67,6 +70,18 @@ class PoseService:
         with self._lock, torch.no_grad():
             people = process(image, self.model, self.config, self.params,
                              self.model_params)
+        return self._people_dicts(people)
+
+    def infer_many(self, images):
+        """list of (H, W, 3) float32 images in [0,1] (sizes may differ) ->
+        one list of people dicts per image, via the batched pipeline."""
+        with self._lock, torch.no_grad():
+            batch = process_batch(list(images), self.model, self.config,
+                                  self.params, self.model_params)
+        return [self._people_dicts(people) for people in batch]
+
+    @staticmethod
+    def _people_dicts(people):
         out = []
         for kps, score in people:
             out.append({
@@ -90,12 +105,35 @@ def decode_image(data: bytes, content_type: str = "") -> np.ndarray:
         from PIL import Image
         arr = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"),
                          dtype=np.float32) / 255.0
+    return _as_image(arr)
+
+
+def _as_image(arr) -> np.ndarray:
     arr = np.asarray(arr, dtype=np.float32)
     if arr.ndim != 3 or arr.shape[2] != 3:
         raise ValueError(f"expected (H, W, 3) image, got {arr.shape}")
     if arr.max() > 1.5:  # 0..255 input
         arr = arr / 255.0
     return np.ascontiguousarray(arr)
+
+
+def decode_image_batch(data: bytes, content_type: str = ""):
+    """Accept an (N, H, W, 3) .npy array or a JSON list of nested-list images
+    (or ``{"images": [...]}``); images of a JSON list may differ in size."""
+    if data[:6] == b"\x93NUMPY":
+        arr = np.load(io.BytesIO(data), allow_pickle=False)
+        if arr.ndim != 4:
+            raise ValueError(f"expected (N, H, W, 3) images, got {arr.shape}")
+        items = list(arr)
+    elif content_type.startswith("application/json") or data[:1] in (b"[", b"{"):
+        import json
+        obj = json.loads(data)
+        items = obj["images"] if isinstance(obj, dict) else obj
+        if not isinstance(items, list):
+            raise ValueError("expected a JSON list of images")
+    else:
+        raise ValueError("expected a .npy array or a JSON list of images")
+    return [_as_image(item) for item in items]
 
 
 def create_app(service: Optional[PoseService] = None, **service_kwargs):
@@ -134,5 +172,17 @@ def create_app(service: Optional[PoseService] = None, **service_kwargs):
             return {"error": str(e)}
         people = svc.infer(img)
         return {"people": people, "image_size": list(img.shape[:2])}
+
+    @app.post("/pose_batch")
+    async def pose_batch(request: Request, response: Response):
+        data = await request.body()
+        try:
+            imgs = decode_image_batch(data,
+                                      request.headers.get("content-type", ""))
+        except Exception as e:
+            response.status_code = 400
+            return {"error": str(e)}
+        return [{"people": people, "image_size": list(img.shape[:2])}
+                for img, people in zip(imgs, svc.infer_many(imgs))]
 
     return app

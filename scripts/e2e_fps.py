@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from improved_body_parts_amd.config import GetConfig, TrainingOpt, InferenceParams
 from improved_body_parts_amd.data import SyntheticPoseDataset
-from improved_body_parts_amd.engine.inference import process
+from improved_body_parts_amd.engine.inference import process, process_batch
 from improved_body_parts_amd.models import NetworkEval
 
 import argparse
@@ -14,6 +14,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--train-steps", type=int, default=300,
                 help="brief training first so the pipeline sees REAL peaks "
                      "(random-init nets produce none and make assembly free)")
+ap.add_argument("--batch", type=int, nargs="+", default=[1],
+                help="images per process_batch() call; 1 = per-image process(). "
+                     "Several values are measured in turn on the same model")
+ap.add_argument("--images", type=int, default=24, help="images per timed pass")
+ap.add_argument("--repeats", type=int, default=1, help="timed passes per --batch")
 args = ap.parse_args()
 
 config = GetConfig("Canonical")
@@ -57,15 +62,39 @@ if args.train_steps:
 model.eval()
 p, mp = InferenceParams().as_params_dict()
 ds = SyntheticPoseDataset(config, length=64, render=True, seed=3)
-imgs = [ds.generate(i)[0] for i in range(24)]
-for img in imgs[:4]:
-    process(img, model, config, p, mp)          # warmup
-torch.cuda.synchronize(); t0 = time.perf_counter()
-n_people = 0
-for img in imgs:
-    n_people += len(process(img, model, config, p, mp))
-torch.cuda.synchronize()
-dt = time.perf_counter() - t0
-print(f"end-to-end process() {len(imgs)/dt:.1f} img/s over {len(imgs)} images "
-      f"({n_people} people found; 512^2, {opt.nstack}-stack, single scale, "
-      f"flip ensemble, {'trained ' + str(args.train_steps) + ' steps' if args.train_steps else 'random-init'})")
+imgs = [ds.generate(i % 64)[0] for i in range(args.images)]
+
+
+def measure(batch_size):
+    """Warm up, then time one pass over ``imgs``; returns (img/s, people)."""
+    if batch_size > 1:
+        def run(batch):
+            return sum(len(r) for r in process_batch(batch, model, config, p, mp))
+        chunks = [imgs[i:i + batch_size] for i in range(0, len(imgs), batch_size)]
+        # warm every batch size the timed loop uses
+        for n in sorted({len(c) for c in chunks}):
+            run(imgs[:n])
+    else:
+        def run(batch):
+            return len(process(batch[0], model, config, p, mp))
+        chunks = [[img] for img in imgs]
+        for img in imgs[:4]:
+            run([img])                               # warmup
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    n_people = 0
+    for chunk in chunks:
+        n_people += run(chunk)
+    torch.cuda.synchronize()
+    return len(imgs) / (time.perf_counter() - t0), n_people
+
+
+# several --batch values alternate inside each repeat, so they see the same
+# machine state and their spread can be compared
+for rep in range(args.repeats):
+    for b in args.batch:
+        fps, n_people = measure(b)
+        label = f"process_batch(batch={b})" if b > 1 else "process()"
+        print(f"end-to-end {label} {fps:.1f} img/s over {len(imgs)} images "
+              f"({n_people} people found; 512^2, {opt.nstack}-stack, single scale, "
+              f"flip ensemble, {'trained ' + str(args.train_steps) + ' steps' if args.train_steps else 'random-init'})",
+              flush=True)
