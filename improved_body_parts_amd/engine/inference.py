@@ -22,6 +22,9 @@ MI355X-first design differences from the reference (behavior preserved):
     (reference README.md:68).
   * Everything falls back to the same torch ops on CPU so the pipeline is
     unit-testable without a GPU.
+  * Every stage is written once, for a list of images and a planar
+    (N, heat + paf, H, W) buffer; ``predict``, ``find_peaks``,
+    ``find_connections`` and ``process`` are the N = 1 wrappers.
 """
 from __future__ import annotations
 
@@ -57,156 +60,178 @@ def _to_device_image(image, device, dtype=torch.float32):
     return t
 
 
-def _resize_hwc(t, out_h, out_w):
-    """Bicubic resize of an (H, W, C) tensor (reference cv2.INTER_CUBIC)."""
-    x = t.permute(2, 0, 1)[None]
-    x = F.interpolate(x, size=(out_h, out_w), mode="bicubic", align_corners=False)
-    return x[0].permute(1, 2, 0)
-
-
-def _rotate_hwc(t, angle_deg, inverse=False):
-    """Rotate an (H, W, C) tensor about its center (reference cv2.warpAffine
+def _rotate_nchw(x, angle_deg, inverse=False):
+    """Rotate an (N, C, H, W) batch about its center (reference cv2.warpAffine
     with getRotationMatrix2D; the reference passes (h/2, w/2) as the cv2
     center which is an x/y mix-up for non-square inputs — inputs there are
     always padded square; we rotate about the true center)."""
     if angle_deg == 0:
-        return t
+        return x
     a = math.radians(angle_deg if not inverse else -angle_deg)
     cos, sin = math.cos(a), math.sin(a)
     # grid_sample samples the INPUT at the transformed output coordinates, so
     # the theta matrix is the inverse rotation; normalized coords are square
-    # here only if H == W, so fold the aspect ratio in explicitly.
-    H, W = t.shape[0], t.shape[1]
-    # aspect handling in normalized coords: x' = cos*x - sin*(y*H/W);
-    # y' = sin*(x*W/H) + cos*y
+    # only if H == W, so fold the aspect ratio in explicitly:
+    # x' = cos*x - sin*(y*H/W); y' = sin*(x*W/H) + cos*y
+    H, W = x.shape[2], x.shape[3]
     theta = torch.tensor([[cos, -sin * H / W, 0.0],
                           [sin * W / H, cos, 0.0]],
-                         dtype=torch.float32, device=t.device)
-    x = t.permute(2, 0, 1)[None].float()
-    grid = F.affine_grid(theta[None], x.shape, align_corners=False)
-    out = F.grid_sample(x, grid, mode="bilinear", padding_mode="zeros",
+                         dtype=torch.float32, device=x.device)
+    xf = x.float()
+    grid = F.affine_grid(theta[None].expand(x.shape[0], -1, -1), xf.shape,
+                         align_corners=False)
+    out = F.grid_sample(xf, grid, mode="bilinear", padding_mode="zeros",
                         align_corners=False)
-    return out[0].permute(1, 2, 0).to(t.dtype)
+    return out.to(x.dtype)
 
 
-# --------------------------------------------------------------------------
-# predict: multi-scale / rotation / flip ensemble forward
-# --------------------------------------------------------------------------
-
-@torch.no_grad()
-def predict(image, model, config: CanonicalConfig, params=None, model_params=None,
-            device=None, dtype=None):
-    """Run the ensemble forward (reference evaluate.py:83-161).
-
-    Returns ``(heatmap_avg, paf_avg)`` as (H, W, C) fp32 torch tensors at the
-    ORIGINAL image resolution, on ``device`` (stays on GPU when one is used).
-    """
+def _resolve_params(params, model_params):
+    """Fill missing ``params`` / ``model_params`` from ``InferenceParams``."""
     if params is None or model_params is None:
         p, mp = InferenceParams().as_params_dict()
         params = params or p
         model_params = model_params or mp
+    return params, model_params
+
+
+def _scaled_geometry(H, W, scale, pad_to):
+    """``(sh, sw, pad_h, pad_w)``: the size an (H, W) image is resized to at
+    ``scale`` and the right/bottom padding up to a multiple of ``pad_to``."""
+    # cap absurdly large upscales (reference evaluate.py:94-96)
+    if scale * H > 2600 or scale * W > 3800:
+        scale = min(2600 / H, 3800 / W)
+    sh, sw = max(int(round(H * scale)), 1), max(int(round(W * scale)), 1)
+    return sh, sw, (pad_to - sh % pad_to) % pad_to, (pad_to - sw % pad_to) % pad_to
+
+
+# --------------------------------------------------------------------------
+# predict: multi-scale / rotation / flip ensemble forward, many images per
+# forward, fused ensemble merge
+# --------------------------------------------------------------------------
+
+def _output_channels(config: CanonicalConfig):
+    """``(chan_order, flip_perm)``: where the ``[heat | paf]`` output channels
+    sit in the network's ``[paf | heat]`` output, and the L/R permutation of the
+    mirrored view in that output order."""
+    n_heat = config.num_layers - config.paf_layers
+    n_paf = config.paf_layers
+    chan_order = list(range(n_paf, n_paf + n_heat)) + list(range(n_paf))
+    flip_perm = [int(c) for c in config.flip_heat_ord] + \
+        [n_heat + int(c) for c in config.flip_paf_ord]
+    return chan_order, flip_perm
+
+
+@torch.no_grad()
+def _predict_groups(images, model, config, params, model_params, max_views,
+                    device=None, dtype=None):
+    """Ensemble forward of a list of images (reference evaluate.py:83-161).
+    Returns ``[(indices, maps)]``, one entry per distinct image size: ``maps``
+    is the planar fp32 (n, heat + paf, H, W) average of the images ``indices``
+    in that order."""
+    params, model_params = _resolve_params(params, model_params)
     if device is None:
         device = next(model.parameters()).device
     if dtype is None:
         dtype = next(model.parameters()).dtype
+    if max_views < 2:
+        raise ValueError("max_views must allow an image and its mirror (>= 2)")
+    chunk = max_views // 2
 
-    img = _to_device_image(image, device)
-    H, W = img.shape[0], img.shape[1]
-    flip_heat = torch.as_tensor(np.asarray(config.flip_heat_ord), device=device,
-                                dtype=torch.long)
-    flip_paf = torch.as_tensor(np.asarray(config.flip_paf_ord), device=device,
-                               dtype=torch.long)
-    n_heat = config.num_layers - config.paf_layers  # 18 + 2
-    n_paf = config.paf_layers
-    heatmap_avg = torch.zeros(H, W, n_heat, device=device)
-    paf_avg = torch.zeros(H, W, n_paf, device=device)
-
-    multiplier = [s * model_params["boxsize"] / H for s in params["scale_search"]]
+    chan_order, flip_perm = _output_channels(config)
     rotations = params.get("rotation_search", [0.0])
     pad_to = model_params["max_downsample"]
     pad_value = model_params["padValue"] / 255.0
 
-    for scale in multiplier:
-        # cap absurdly large upscales (reference evaluate.py:94-96)
-        if scale * H > 2600 or scale * W > 3800:
-            scale = min(2600 / H, 3800 / W)
-        for angle in rotations:
-            sh, sw = max(int(round(H * scale)), 1), max(int(round(W * scale)), 1)
-            scaled = _resize_hwc(img, sh, sw)
-            pad_h = (pad_to - sh % pad_to) % pad_to
-            pad_w = (pad_to - sw % pad_to) % pad_to
-            padded = F.pad(scaled.permute(2, 0, 1), (0, pad_w, 0, pad_h),
-                           value=pad_value).permute(1, 2, 0)
-            if angle != 0:
-                padded = _rotate_hwc(padded, angle)
-            flipped = torch.flip(padded, dims=[1])
-            batch = torch.stack([padded, flipped]).to(dtype)     # (2, h, w, 3) NHWC
+    by_size = {}
+    for i, image in enumerate(images):
+        img = _to_device_image(image, device)
+        by_size.setdefault((img.shape[0], img.shape[1]), []).append((i, img))
 
-            out = model(batch)
-            out = out[-1][0].float()                             # last stack, scale 0
-            paf = out[:, :n_paf]
-            heat = out[:, n_paf:n_paf + n_heat]
+    groups = []
+    for (H, W), members in by_size.items():
+        idxs = [i for i, _ in members]
+        imgs = torch.stack([t for _, t in members]).permute(0, 3, 1, 2)  # NCHW
+        n = len(idxs)
+        maps = torch.empty(n, len(chan_order), H, W, device=device,
+                           dtype=torch.float32)
+        multiplier = [s * model_params["boxsize"] / H
+                      for s in params["scale_search"]]
+        n_runs = len(multiplier) * len(rotations)
+        first = True
+        for scale in multiplier:
+            sh, sw, pad_h, pad_w = _scaled_geometry(H, W, scale, pad_to)
+            scaled = F.interpolate(imgs, size=(sh, sw), mode="bicubic",
+                                   align_corners=False)
+            padded0 = F.pad(scaled, (0, pad_w, 0, pad_h), value=pad_value)
+            ph, pw = padded0.shape[2], padded0.shape[3]
+            for angle in rotations:
+                padded = _rotate_nchw(padded0, angle)
+                flipped = torch.flip(padded, dims=[3])
+                for lo in range(0, n, chunk):
+                    hi = min(lo + chunk, n)
+                    batch = torch.cat([padded[lo:hi], flipped[lo:hi]]) \
+                        .permute(0, 2, 3, 1).contiguous().to(dtype)   # NHWC
+                    out = model(batch)[-1][0]            # last stack, scale 0
+                    stride = ph // out.shape[2]
+                    assert out.shape[2] * stride == ph and \
+                        out.shape[3] * stride == pw, "non-integer output stride"
+                    if angle == 0:
+                        ensemble_merge(out, flip_perm, stride, (sh, sw), (H, W),
+                                       scale=1.0 / n_runs, out=maps[lo:hi],
+                                       accumulate=not first,
+                                       chan_order=chan_order)
+                        continue
+                    # rotated runs keep the torch chain, batched along N
+                    v = out.float()[:, chan_order]
+                    merged = (v[:hi - lo] +
+                              torch.flip(v[hi - lo:], dims=[-1])[:, flip_perm]) * 0.5
+                    up = F.interpolate(merged, size=(ph, pw), mode="bicubic",
+                                       align_corners=False)
+                    up = _rotate_nchw(up, angle, inverse=True)[:, :, :sh, :sw]
+                    up = F.interpolate(up, size=(H, W), mode="bicubic",
+                                       align_corners=False) / n_runs
+                    if first:
+                        maps[lo:hi] = up
+                    else:
+                        maps[lo:hi] += up
+                first = False
+        groups.append((idxs, maps))
+    return groups
 
-            # flip ensemble: mirror the flipped copy back and permute L/R channels
-            paf_f = torch.flip(paf[1], dims=[-1])[flip_paf]
-            heat_f = torch.flip(heat[1], dims=[-1])[flip_heat]
-            paf = (paf[0] + paf_f) * 0.5
-            heat = (heat[0] + heat_f) * 0.5
 
-            # x stride upsample, unrotate, unpad, resize to original
-            ph, pw = padded.shape[0], padded.shape[1]
-            up = F.interpolate(torch.cat([heat, paf])[None], size=(ph, pw),
-                               mode="bicubic", align_corners=False)[0]
-            if angle != 0:
-                up = _rotate_hwc(up.permute(1, 2, 0), angle, inverse=True) \
-                    .permute(2, 0, 1)
-            up = up[:, :sh, :sw]
-            up = F.interpolate(up[None], size=(H, W), mode="bicubic",
-                               align_corners=False)[0].permute(1, 2, 0)
+def predict_batch(images, model, config: CanonicalConfig, params=None,
+                  model_params=None, max_views=16, device=None, dtype=None):
+    """Run the ensemble forward over a list of (H, W, 3) images.
 
-            n_runs = len(multiplier) * len(rotations)
-            heatmap_avg += up[..., :n_heat] / n_runs
-            paf_avg += up[..., n_heat:] / n_runs
+    Images are grouped by size; per scale and rotation each group goes through
+    the model as ``[views | mirrored views]`` in chunks of at most ``max_views``
+    views, and rotation-free runs are merged by the fused ``ensemble_merge``
+    kernel. Returns one ``(heatmap_avg, paf_avg)`` per image in input order:
+    (H, W, C) fp32 views, at the ORIGINAL image resolution, of the group's
+    planar buffer on ``device`` (stays on GPU when one is used).
+    """
+    n_heat = config.num_layers - config.paf_layers
+    results = [None] * len(images)
+    for idxs, maps in _predict_groups(images, model, config, params,
+                                      model_params, max_views, device, dtype):
+        for j, i in enumerate(idxs):
+            results[i] = (maps[j, :n_heat].permute(1, 2, 0),
+                          maps[j, n_heat:].permute(1, 2, 0))
+    return results
 
-    return heatmap_avg, paf_avg
+
+def predict(image, model, config: CanonicalConfig, params=None, model_params=None,
+            device=None, dtype=None):
+    """``predict_batch`` for one image: ``(heatmap_avg, paf_avg)`` as (H, W, C)
+    fp32 tensors on ``device``. The two are views of one planar
+    (heat + paf, H, W) buffer, not separately allocated tensors."""
+    return predict_batch([image], model, config, params, model_params,
+                         device=device, dtype=dtype)[0]
 
 
 # --------------------------------------------------------------------------
 # find_peaks
 # --------------------------------------------------------------------------
-
-def find_peaks(heatmap_avg, params, config: CanonicalConfig, max_peaks=512):
-    """NMS + sub-pixel refinement over the 18 keypoint channels
-    (reference evaluate.py:169-203). ``heatmap_avg``: (H, W, C) torch tensor.
-
-    Returns the reference's ``all_peaks`` structure: a list of ``heat_layers``
-    lists of ``(x, y, score, global_id)`` tuples.
-    """
-    n_parts = config.heat_layers  # 18 keypoint channels (bkg excluded)
-    heat = heatmap_avg[..., :n_parts].permute(2, 0, 1).contiguous().float()
-    radius = int(params["offset_radius"])
-    thre1 = float(params["thre1"])
-
-    rows = []
-    if use_hip_for(heat):
-        ext = hip_extension()
-        nmsed = ext.heatmap_nms(heat, thre1)
-        out, cnt = ext.collect_peaks(nmsed, heat, radius, max_peaks)
-        n = min(int(cnt.item()), max_peaks)
-        rows = out[:n].cpu().numpy()
-        # atomics make device order nondeterministic: impose (c, y, x) order
-        rows = rows[np.lexsort((rows[:, 1], rows[:, 2], rows[:, 0]))]
-    else:
-        nmsed = keypoint_heatmap_nms(heat[None], kernel=3, thre=thre1)[0]
-        heat_np = heat.cpu().numpy()
-        for c in range(n_parts):
-            ys, xs = np.nonzero(nmsed[c].cpu().numpy())
-            for y, x in zip(ys, xs):
-                xr, yr, sc = refine_centroid(heat_np[c], (int(x), int(y)), radius)
-                rows.append((c, xr, yr, sc, heat_np[c, y, x]))
-        rows = np.asarray(rows, dtype=np.float32).reshape(-1, 5)
-    return _rows_to_peaks(rows, n_parts)
-
 
 def _rows_to_peaks(rows, n_parts):
     """(c, x, y, score, peak) rows in (c, y, x) order -> ``all_peaks``."""
@@ -215,6 +240,51 @@ def _rows_to_peaks(rows, n_parts):
         c = int(row[0])
         all_peaks[c].append((float(row[1]), float(row[2]), float(row[3]), gid))
     return all_peaks
+
+
+def find_peaks_batch(maps, params, config: CanonicalConfig, max_peaks=512):
+    """NMS + sub-pixel refinement over the 18 keypoint channels (reference
+    evaluate.py:169-203) of every image of a planar (N, planes, H, W) buffer
+    whose first ``heat_layers`` planes are the keypoint maps: one kernel launch
+    and one device->host copy for the batch.
+
+    Returns one ``all_peaks`` per image, the reference's structure: a list of
+    ``heat_layers`` lists of ``(x, y, score, id)`` tuples, ids per image.
+    """
+    n_parts = config.heat_layers  # 18 keypoint channels (bkg excluded)
+    radius = int(params["offset_radius"])
+    thre1 = float(params["thre1"])
+    maps = maps.contiguous().float()
+    out = []
+    if use_hip_for(maps):
+        buf = hip_extension().peaks_batched(maps, n_parts, thre1, radius,
+                                            max_peaks).cpu().numpy()
+        counts = np.ascontiguousarray(buf[:, 0, 0]).view(np.int32)
+        for n in range(buf.shape[0]):
+            rows = buf[n, 1:1 + min(int(counts[n]), max_peaks)]
+            # atomics make device order nondeterministic: impose (c, y, x) order
+            rows = rows[np.lexsort((rows[:, 1], rows[:, 2], rows[:, 0]))]
+            out.append(_rows_to_peaks(rows, n_parts))
+        return out
+    heat = maps[:, :n_parts]
+    nmsed = keypoint_heatmap_nms(heat, kernel=3, thre=thre1).cpu().numpy()
+    heat_np = heat.cpu().numpy()
+    for n in range(heat_np.shape[0]):
+        rows = []
+        for c in range(n_parts):
+            ys, xs = np.nonzero(nmsed[n, c])
+            for y, x in zip(ys, xs):
+                xr, yr, sc = refine_centroid(heat_np[n, c], (int(x), int(y)), radius)
+                rows.append((c, xr, yr, sc, heat_np[n, c, y, x]))
+        rows = np.asarray(rows, dtype=np.float32).reshape(-1, 5)
+        out.append(_rows_to_peaks(rows, n_parts))
+    return out
+
+
+def find_peaks(heatmap_avg, params, config: CanonicalConfig, max_peaks=512):
+    """``find_peaks_batch`` for one (H, W, C) torch map."""
+    heat = heatmap_avg[..., :config.heat_layers].permute(2, 0, 1)[None]
+    return find_peaks_batch(heat, params, config, max_peaks)[0]
 
 
 # --------------------------------------------------------------------------
@@ -298,43 +368,60 @@ def _greedy_match(all_peaks, scores, pair_meta, params, config: CanonicalConfig)
     return connection_all, special_k
 
 
-def find_connections(all_peaks, paf_avg, image_height, params, config: CanonicalConfig):
-    """Score + greedily match candidate limbs (reference evaluate.py:206-276).
+def find_connections_batch(all_peaks_list, maps, params, config: CanonicalConfig,
+                           first_limb_plane=None):
+    """Score + greedily match candidate limbs (reference evaluate.py:206-276)
+    for every image of a planar (N, planes, H, W) buffer whose limb maps start
+    at plane ``first_limb_plane``: the heat count of a pipeline buffer by
+    default, 0 for bare PAF maps. Every image's (limb_type, peakA, peakB)
+    triples are scored in one kernel launch with one copy back; the greedy 1-1
+    matching per limb type runs per image on the host.
 
-    ``paf_avg``: (H, W, paf_layers) torch tensor (device or CPU). Scoring of
-    every (limb_type, peakA, peakB) triple is one batched HIP kernel launch;
-    the greedy 1-1 matching per limb type stays on the host.
-
-    Returns ``(connection_all, special_k)`` in the reference's format:
-    per limb type either an (n, 6) array ``[idA, idB, score, i, j, length]``
-    or an empty list.
+    Returns one ``(connection_all, special_k)`` per image in the reference's
+    format: per limb type either an (n, 6) array
+    ``[idA, idB, score, i, j, length]`` or an empty list.
     """
+    if first_limb_plane is None:
+        first_limb_plane = config.num_layers - config.paf_layers
     mid_num = int(params["mid_num"])
     thre2 = float(params["thre2"])
-
-    cand_triples, pair_meta = _candidate_triples(all_peaks, config.limbs_conn)
-
-    flat_peaks = [p for sub in all_peaks for p in sub]
-    flat_peaks.sort(key=lambda p: p[3])
-
+    maps = maps.contiguous().float()
+    planes = maps.shape[1]
+    cands, metas, flat_peaks = [], [], []
+    for n, all_peaks in enumerate(all_peaks_list):
+        triples, meta = _candidate_triples(all_peaks, config.limbs_conn)
+        base = len(flat_peaks)
+        flat_peaks.extend(sorted((p for sub in all_peaks for p in sub),
+                                 key=lambda p: p[3]))
+        # scoring picks its plane by the first field: this image's limb k
+        cands.extend((n * planes + first_limb_plane + k, base + ia, base + ib)
+                     for k, ia, ib in triples)
+        metas.append(meta)
     scores = np.zeros((0, 3), dtype=np.float32)
-    if cand_triples:
-        paf = paf_avg.permute(2, 0, 1).contiguous().float()
-        if use_hip_for(paf):
-            ext = hip_extension()
-            peaks_dev = torch.tensor([[0.0, p[0], p[1], p[2], 0.0] for p in flat_peaks],
-                                     dtype=torch.float32, device=paf.device)
-            cand_dev = torch.tensor(cand_triples, dtype=torch.int32, device=paf.device)
-            scores = ext.limb_scores(paf, peaks_dev, cand_dev, mid_num, thre2) \
-                .cpu().numpy()
-        else:
-            paf_np = paf.cpu().numpy()
-            scores = np.array([
-                _limb_scores_host(paf_np[k], flat_peaks[ia], flat_peaks[ib],
-                                  mid_num, thre2)
-                for (k, ia, ib) in cand_triples], dtype=np.float32)
+    if cands and use_hip_for(maps):
+        peaks_dev = torch.tensor([[0.0, p[0], p[1], p[2], 0.0] for p in flat_peaks],
+                                 dtype=torch.float32, device=maps.device)
+        cand_dev = torch.tensor(cands, dtype=torch.int32, device=maps.device)
+        scores = hip_extension().limb_scores(maps, peaks_dev, cand_dev, mid_num,
+                                             thre2).cpu().numpy()
+    elif cands:
+        planes_np = maps.cpu().numpy().reshape(-1, maps.shape[2], maps.shape[3])
+        scores = np.array([
+            _limb_scores_host(planes_np[plane], flat_peaks[ia], flat_peaks[ib],
+                              mid_num, thre2)
+            for (plane, ia, ib) in cands], dtype=np.float32)
+    out, ptr = [], 0
+    for all_peaks, meta in zip(all_peaks_list, metas):
+        out.append(_greedy_match(all_peaks, scores[ptr:ptr + len(meta)], meta,
+                                 params, config))
+        ptr += len(meta)
+    return out
 
-    return _greedy_match(all_peaks, scores, pair_meta, params, config)
+
+def find_connections(all_peaks, paf_avg, image_height, params, config: CanonicalConfig):
+    """``find_connections_batch`` for one (H, W, paf_layers) torch map."""
+    return find_connections_batch([all_peaks], paf_avg.permute(2, 0, 1)[None],
+                                  params, config, first_limb_plane=0)[0]
 
 
 # --------------------------------------------------------------------------
@@ -494,229 +581,13 @@ def subsets_to_keypoints(subset, candidate, config: CanonicalConfig):
 
 
 @torch.no_grad()
-def process(image, model, config: CanonicalConfig, params=None, model_params=None):
-    """Full pipeline for one image -> list of (coco_keypoints, score)
-    (reference evaluate.py:500-542)."""
-    if params is None or model_params is None:
-        p, mp = InferenceParams().as_params_dict()
-        params = params or p
-        model_params = model_params or mp
-    heatmap_avg, paf_avg = predict(image, model, config, params, model_params)
-    all_peaks = find_peaks(heatmap_avg, params, config)
-    connection_all, special_k = find_connections(
-        all_peaks, paf_avg, heatmap_avg.shape[0], params, config)
-    subset, candidate = find_people(connection_all, special_k, all_peaks,
-                                    params, config)
-    return subsets_to_keypoints(subset, candidate, config)
-
-
-# --------------------------------------------------------------------------
-# batched inference: many images per forward, fused ensemble merge, one
-# device->host transfer per post-processing stage
-# --------------------------------------------------------------------------
-
-def _rotate_nchw(x, angle_deg, inverse=False):
-    """``_rotate_hwc`` for an (N, C, H, W) batch."""
-    if angle_deg == 0:
-        return x
-    a = math.radians(angle_deg if not inverse else -angle_deg)
-    cos, sin = math.cos(a), math.sin(a)
-    H, W = x.shape[2], x.shape[3]
-    theta = torch.tensor([[cos, -sin * H / W, 0.0],
-                          [sin * W / H, cos, 0.0]],
-                         dtype=torch.float32, device=x.device)
-    xf = x.float()
-    grid = F.affine_grid(theta[None].expand(x.shape[0], -1, -1), xf.shape,
-                         align_corners=False)
-    out = F.grid_sample(xf, grid, mode="bilinear", padding_mode="zeros",
-                        align_corners=False)
-    return out.to(x.dtype)
-
-
-def _output_channels(config: CanonicalConfig):
-    """``(chan_order, flip_perm)``: where the ``[heat | paf]`` output channels
-    sit in the network's ``[paf | heat]`` output, and the L/R permutation of the
-    mirrored view in that output order."""
-    n_heat = config.num_layers - config.paf_layers
-    n_paf = config.paf_layers
-    chan_order = list(range(n_paf, n_paf + n_heat)) + list(range(n_paf))
-    flip_perm = [int(c) for c in config.flip_heat_ord] + \
-        [n_heat + int(c) for c in config.flip_paf_ord]
-    return chan_order, flip_perm
-
-
-@torch.no_grad()
-def _predict_groups(images, model, config, params, model_params, max_views,
-                    device=None, dtype=None):
-    """Ensemble forward of a list of images. Returns ``[(indices, maps)]``, one
-    entry per distinct image size: ``maps`` is the planar fp32
-    (n, heat + paf, H, W) average of the images ``indices`` in that order."""
-    if params is None or model_params is None:
-        p, mp = InferenceParams().as_params_dict()
-        params = params or p
-        model_params = model_params or mp
-    if device is None:
-        device = next(model.parameters()).device
-    if dtype is None:
-        dtype = next(model.parameters()).dtype
-    if max_views < 2:
-        raise ValueError("max_views must allow an image and its mirror (>= 2)")
-    chunk = max_views // 2
-
-    chan_order, flip_perm = _output_channels(config)
-    rotations = params.get("rotation_search", [0.0])
-    pad_to = model_params["max_downsample"]
-    pad_value = model_params["padValue"] / 255.0
-
-    by_size = {}
-    for i, image in enumerate(images):
-        img = _to_device_image(image, device)
-        by_size.setdefault((img.shape[0], img.shape[1]), []).append((i, img))
-
-    groups = []
-    for (H, W), members in by_size.items():
-        idxs = [i for i, _ in members]
-        imgs = torch.stack([t for _, t in members]).permute(0, 3, 1, 2)  # NCHW
-        n = len(idxs)
-        maps = torch.empty(n, len(chan_order), H, W, device=device,
-                           dtype=torch.float32)
-        multiplier = [s * model_params["boxsize"] / H
-                      for s in params["scale_search"]]
-        n_runs = len(multiplier) * len(rotations)
-        first = True
-        for scale in multiplier:
-            # cap absurdly large upscales (reference evaluate.py:94-96)
-            if scale * H > 2600 or scale * W > 3800:
-                scale = min(2600 / H, 3800 / W)
-            sh, sw = max(int(round(H * scale)), 1), max(int(round(W * scale)), 1)
-            scaled = F.interpolate(imgs, size=(sh, sw), mode="bicubic",
-                                   align_corners=False)
-            pad_h = (pad_to - sh % pad_to) % pad_to
-            pad_w = (pad_to - sw % pad_to) % pad_to
-            padded0 = F.pad(scaled, (0, pad_w, 0, pad_h), value=pad_value)
-            ph, pw = padded0.shape[2], padded0.shape[3]
-            for angle in rotations:
-                padded = _rotate_nchw(padded0, angle)
-                flipped = torch.flip(padded, dims=[3])
-                for lo in range(0, n, chunk):
-                    hi = min(lo + chunk, n)
-                    batch = torch.cat([padded[lo:hi], flipped[lo:hi]]) \
-                        .permute(0, 2, 3, 1).contiguous().to(dtype)   # NHWC
-                    out = model(batch)[-1][0]            # last stack, scale 0
-                    stride = ph // out.shape[2]
-                    assert out.shape[2] * stride == ph and \
-                        out.shape[3] * stride == pw, "non-integer output stride"
-                    if angle == 0:
-                        ensemble_merge(out, flip_perm, stride, (sh, sw), (H, W),
-                                       scale=1.0 / n_runs, out=maps[lo:hi],
-                                       accumulate=not first,
-                                       chan_order=chan_order)
-                        continue
-                    # rotated runs keep the torch chain, batched along N
-                    v = out.float()[:, chan_order]
-                    merged = (v[:hi - lo] +
-                              torch.flip(v[hi - lo:], dims=[-1])[:, flip_perm]) * 0.5
-                    up = F.interpolate(merged, size=(ph, pw), mode="bicubic",
-                                       align_corners=False)
-                    up = _rotate_nchw(up, angle, inverse=True)[:, :, :sh, :sw]
-                    up = F.interpolate(up, size=(H, W), mode="bicubic",
-                                       align_corners=False) / n_runs
-                    if first:
-                        maps[lo:hi] = up
-                    else:
-                        maps[lo:hi] += up
-                first = False
-        groups.append((idxs, maps))
-    return groups
-
-
-def predict_batch(images, model, config: CanonicalConfig, params=None,
-                  model_params=None, max_views=16, device=None, dtype=None):
-    """``predict`` for a list of (H, W, 3) images.
-
-    Images are grouped by size; per scale and rotation each group goes through
-    the model as ``[views | mirrored views]`` in chunks of at most ``max_views``
-    views, and rotation-free runs are merged by the fused ``ensemble_merge``
-    kernel. Returns one ``(heatmap_avg, paf_avg)`` per image in input order,
-    laid out as ``predict`` returns them: (H, W, C) views of a planar buffer.
-    """
-    n_heat = config.num_layers - config.paf_layers
-    results = [None] * len(images)
-    for idxs, maps in _predict_groups(images, model, config, params,
-                                      model_params, max_views, device, dtype):
-        for j, i in enumerate(idxs):
-            results[i] = (maps[j, :n_heat].permute(1, 2, 0),
-                          maps[j, n_heat:].permute(1, 2, 0))
-    return results
-
-
-def find_peaks_batch(maps, params, config: CanonicalConfig, max_peaks=512):
-    """``find_peaks`` over a planar (N, heat + paf, H, W) fp32 buffer: one
-    kernel launch and one device->host copy for the batch. Returns one
-    ``all_peaks`` per image (peak ids are per image, as in ``find_peaks``)."""
-    n_parts = config.heat_layers
-    if not use_hip_for(maps):
-        return [find_peaks(maps[n, :n_parts].permute(1, 2, 0), params, config,
-                           max_peaks) for n in range(maps.shape[0])]
-    buf = hip_extension().peaks_batched(
-        maps.contiguous(), n_parts, float(params["thre1"]),
-        int(params["offset_radius"]), max_peaks).cpu().numpy()
-    counts = np.ascontiguousarray(buf[:, 0, 0]).view(np.int32)
-    out = []
-    for n in range(buf.shape[0]):
-        rows = buf[n, 1:1 + min(int(counts[n]), max_peaks)]
-        # atomics make device order nondeterministic: impose (c, y, x) order
-        rows = rows[np.lexsort((rows[:, 1], rows[:, 2], rows[:, 0]))]
-        out.append(_rows_to_peaks(rows, n_parts))
-    return out
-
-
-def find_connections_batch(all_peaks_list, maps, params, config: CanonicalConfig):
-    """``find_connections`` for every image of a planar (N, heat + paf, H, W)
-    buffer: all images' candidates are scored in one kernel launch with one
-    copy back; the greedy matching runs per image on the host."""
-    n_heat = config.num_layers - config.paf_layers
-    if not use_hip_for(maps):
-        return [find_connections(pk, maps[n, n_heat:].permute(1, 2, 0),
-                                 maps.shape[2], params, config)
-                for n, pk in enumerate(all_peaks_list)]
-    maps = maps.contiguous()
-    planes = maps.shape[1]
-    cands, metas, peak_rows = [], [], []
-    for n, all_peaks in enumerate(all_peaks_list):
-        triples, meta = _candidate_triples(all_peaks, config.limbs_conn)
-        base = len(peak_rows)
-        flat = sorted((p for sub in all_peaks for p in sub), key=lambda p: p[3])
-        peak_rows.extend([0.0, p[0], p[1], p[2], 0.0] for p in flat)
-        # the kernel picks its plane by the first field: this image's limb k
-        cands.extend((n * planes + n_heat + k, base + ia, base + ib)
-                     for k, ia, ib in triples)
-        metas.append(meta)
-    scores = np.zeros((0, 3), dtype=np.float32)
-    if cands:
-        peaks_dev = torch.tensor(peak_rows, dtype=torch.float32, device=maps.device)
-        cand_dev = torch.tensor(cands, dtype=torch.int32, device=maps.device)
-        scores = hip_extension().limb_scores(
-            maps, peaks_dev, cand_dev, int(params["mid_num"]),
-            float(params["thre2"])).cpu().numpy()
-    out, ptr = [], 0
-    for all_peaks, meta in zip(all_peaks_list, metas):
-        out.append(_greedy_match(all_peaks, scores[ptr:ptr + len(meta)], meta,
-                                 params, config))
-        ptr += len(meta)
-    return out
-
-
-@torch.no_grad()
 def process_batch(images, model, config: CanonicalConfig, params=None,
                   model_params=None, max_views=16):
-    """``process`` for a list of images: batched forward and ensemble merge,
-    batched peak and limb kernels, then the per-image greedy assembly. Returns
-    one ``process`` result per image, in input order."""
-    if params is None or model_params is None:
-        p, mp = InferenceParams().as_params_dict()
-        params = params or p
-        model_params = model_params or mp
+    """Full pipeline for a list of images (reference evaluate.py:500-542):
+    batched forward and ensemble merge, batched peak and limb kernels, then the
+    per-image greedy assembly. Returns one list of (coco_keypoints, score) per
+    image, in input order."""
+    params, model_params = _resolve_params(params, model_params)
     results = [None] * len(images)
     for idxs, maps in _predict_groups(images, model, config, params,
                                       model_params, max_views):
@@ -727,6 +598,11 @@ def process_batch(images, model, config: CanonicalConfig, params=None,
                                             params, config)
             results[i] = subsets_to_keypoints(subset, candidate, config)
     return results
+
+
+def process(image, model, config: CanonicalConfig, params=None, model_params=None):
+    """``process_batch`` for one image -> list of (coco_keypoints, score)."""
+    return process_batch([image], model, config, params, model_params)[0]
 
 
 def format_results(keypoints, res_file):

@@ -229,17 +229,3 @@ def focal_l2_loss(pred, gt, mask, *, heat_start, bkg_start, gamma=1,
     loss_nstack = out.sum(dim=(1, 2, 3, 4))
     w = [loss_nstack[i] * nstack_weight[i] for i in range(nstack)]
     return sum(w) / sum(nstack_weight)
-
-
-# ---------------------------------------------------------------------------
-# post-processing primitives (device path wired up in ops/postproc.py)
-# ---------------------------------------------------------------------------
-
-def heatmap_nms(heat, threshold=0.1):
-    """3x3 max-pool equality peak mask (reference utils/util.py:177-183)."""
-    if use_hip_for(heat):
-        from . import postproc
-        return postproc.heatmap_nms_hip(heat, threshold)
-    maxm = F.max_pool2d(heat, 3, 1, 1)
-    maxm = torch.eq(maxm, heat).to(heat.dtype)
-    return heat * maxm * (heat > threshold).to(heat.dtype)

@@ -101,9 +101,6 @@ Tensor heatmap_gt(const Tensor& joints, const c10::optional<Tensor>& mask_all,
                   double keypoint_thre, double limb_thre, double paf_thre);
 
 // postproc.hip
-Tensor heatmap_nms(const Tensor& heat, double thre);
-std::vector<Tensor> collect_peaks(const Tensor& nmsed, const Tensor& smoothed,
-                                  int64_t radius, int64_t max_peaks);
 Tensor limb_scores(const Tensor& paf, const Tensor& peaks, const Tensor& cand_idx,
                    int64_t mid_num, double thre2);
 Tensor peaks_batched(const Tensor& maps, int64_t heat_layers, double thre,
@@ -170,8 +167,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bkg_start"), py::arg("num_layers"), py::arg("sigma"),
         py::arg("paf_sigma"), py::arg("keypoint_thre"), py::arg("limb_thre"),
         py::arg("paf_thre"));
-  m.def("heatmap_nms", &heatmap_nms);
-  m.def("collect_peaks", &collect_peaks);
   m.def("limb_scores", &limb_scores);
   m.def("peaks_batched", &peaks_batched,
         "fused NMS + centroid refinement over a planar batch, per-image counters",

@@ -11,80 +11,14 @@
 
 namespace ibp {
 
-// 3x3 max-pool-equality NMS with reflect border + threshold; NCHW layout
-// (post-processing operates on the resized NCHW heatmaps).
-template <typename T>
-__global__ void nms3x3_kernel(const T* __restrict__ heat, T* __restrict__ out,
-                              int NC, int H, int W, float thre) {
-  long long total = (long long)NC * H * W;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    int w = (int)(i % W);
-    long long q = i / W;
-    int h = (int)(q % H);
-    int nc = (int)(q / H);
-    const T* plane = heat + (long long)nc * H * W;
-    float v = ldf(plane + (long long)h * W + w);
-    float m = -1e30f;
-    #pragma unroll
-    for (int dy = -1; dy <= 1; ++dy) {
-      #pragma unroll
-      for (int dx = -1; dx <= 1; ++dx) {
-        int hh = h + dy, ww = w + dx;
-        hh = hh < 0 ? -hh : (hh >= H ? 2 * H - hh - 2 : hh);  // reflect
-        ww = ww < 0 ? -ww : (ww >= W ? 2 * W - ww - 2 : ww);
-        m = fmaxf(m, ldf(plane + (long long)hh * W + ww));
-      }
-    }
-    stf(out + i, (v == m && v >= thre) ? v : 0.f);
-  }
-}
-
-// collect peaks (nonzero after NMS) with sub-pixel centroid refinement.
-// out rows: [channel, x_refined, y_refined, score_box_mean, peak_score]
-template <typename T>
-__global__ void collect_peaks_kernel(const T* __restrict__ nmsed,
-                                     const T* __restrict__ smoothed,
-                                     float* __restrict__ out, int* __restrict__ cnt,
-                                     int C, int H, int W, int radius, int max_peaks) {
-  long long total = (long long)C * H * W;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    float v = ldf(nmsed + i);
-    if (v <= 0.f) continue;
-    int w = (int)(i % W);
-    long long q = i / W;
-    int h = (int)(q % H);
-    int c = (int)(q / H);
-    int slot = atomicAdd(cnt, 1);
-    if (slot >= max_peaks) continue;
-    // weighted-centroid refinement over (2r+1)^2 (reference util.py:186-211)
-    float xr = (float)w, yr = (float)h, boxmean = v;
-    const T* plane = smoothed + (long long)c * H * W;
-    if (h - radius >= 0 && h + radius < H && w - radius >= 0 && w + radius < W) {
-      float s = 0.f, sx = 0.f, sy = 0.f;
-      for (int dy = -radius; dy <= radius; ++dy)
-        for (int dx = -radius; dx <= radius; ++dx) {
-          float sv = ldf(plane + (long long)(h + dy) * W + (w + dx));
-          s += sv; sx += sv * dx; sy += sv * dy;
-        }
-      if (s > 0.f) {
-        xr = w + sx / s;
-        yr = h + sy / s;
-        boxmean = s / ((2 * radius + 1) * (2 * radius + 1));
-      }
-    }
-    float* row = out + (long long)slot * 5;
-    row[0] = (float)c; row[1] = xr; row[2] = yr; row[3] = boxmean; row[4] = v;
-  }
-}
-
-// Batched peaks: the 3x3 reflect NMS test of nms3x3_kernel and the centroid
-// refinement of collect_peaks_kernel in one pass over the keypoint planes
-// [n][0..C) of a planar (N, planes_per_image, H, W) fp32 buffer. Counters and
-// the max_peaks cap are per image. Image n's block of `out` is
-// [1 + max_peaks][5]: row 0 holds the peak count (as int32 bits) so counts and
-// rows come back in one device->host copy; rows follow in arrival order.
+// Peaks: 3x3 max-pool-equality NMS with reflect border + threshold, and
+// sub-pixel centroid refinement of every survivor, in one pass over the
+// keypoint planes [n][0..C) of a planar (N, planes_per_image, H, W) fp32
+// buffer. Counters and the max_peaks cap are per image. Image n's block of
+// `out` is [1 + max_peaks][5]: row 0 holds the peak count (as int32 bits) so
+// counts and rows come back in one device->host copy; rows
+// [channel, x_refined, y_refined, score_box_mean, peak_score] follow in
+// arrival order.
 __global__ void peaks_batched_kernel(const float* __restrict__ maps,
                                      float* __restrict__ out,
                                      int N, int C, int planes_per_image,
@@ -144,7 +78,7 @@ __global__ void peaks_batched_kernel(const float* __restrict__ maps,
 template <typename T>
 __global__ void limb_score_kernel(
     const T* __restrict__ paf,          // [Cpaf, H, W]
-    const float* __restrict__ peaks,    // [P][5] rows from collect_peaks
+    const float* __restrict__ peaks,    // [P][5] rows as peaks_batched writes
     const int* __restrict__ cand_idx,   // [ncand][3]: limb_id, peakA, peakB
     float* __restrict__ scores,         // [ncand][3]
     int ncand, int H, int W, int mid_num, float thre2) {
@@ -187,42 +121,6 @@ __global__ void limb_score_kernel(
 using torch::Tensor;
 static inline hipStream_t cur_stream4() {
   return at::hip::getCurrentHIPStream().stream();
-}
-
-Tensor heatmap_nms(const Tensor& heat, double thre) {
-  TORCH_CHECK(heat.is_cuda() && heat.is_contiguous());
-  int W = (int)heat.size(-1), H = (int)heat.size(-2);
-  int NC = (int)(heat.numel() / ((long long)H * W));
-  Tensor out = torch::empty_like(heat);
-  dim3 block(256), grid(ibp::grid_1d(heat.numel(), 256, 4096));
-  AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half,
-      heat.scalar_type(), "heatmap_nms", [&] {
-    hipLaunchKernelGGL(ibp::nms3x3_kernel<scalar_t>, grid, block, 0, cur_stream4(),
-                       reinterpret_cast<const scalar_t*>(heat.data_ptr()),
-                       reinterpret_cast<scalar_t*>(out.data_ptr()),
-                       NC, H, W, (float)thre);
-  });
-  return out;
-}
-
-std::vector<Tensor> collect_peaks(const Tensor& nmsed, const Tensor& smoothed,
-                                  int64_t radius, int64_t max_peaks) {
-  int W = (int)nmsed.size(-1), H = (int)nmsed.size(-2);
-  int C = (int)(nmsed.numel() / ((long long)H * W));
-  Tensor out = torch::zeros({max_peaks, 5},
-                            nmsed.options().dtype(torch::kFloat32));
-  Tensor cnt = torch::zeros({1}, nmsed.options().dtype(torch::kInt32));
-  dim3 block(256), grid(ibp::grid_1d(nmsed.numel(), 256, 4096));
-  AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half,
-      nmsed.scalar_type(), "collect_peaks", [&] {
-    hipLaunchKernelGGL(ibp::collect_peaks_kernel<scalar_t>, grid, block, 0,
-                       cur_stream4(),
-                       reinterpret_cast<const scalar_t*>(nmsed.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(smoothed.data_ptr()),
-                       out.data_ptr<float>(), cnt.data_ptr<int>(),
-                       C, H, W, (int)radius, (int)max_peaks);
-  });
-  return {out, cnt};
 }
 
 // maps: planar (N, planes, H, W) fp32; the first `heat_layers` planes of every

@@ -188,7 +188,7 @@ def test_process_end_to_end(config):
 
 @pytest.mark.gpu
 def test_pipeline_device_vs_cpu_parity(config, params):
-    """Device kernels (NMS + collect_peaks + limb_scores) must reproduce the
+    """Device kernels (peaks_batched + limb_scores) must reproduce the
     CPU pipeline on the same synthetic maps."""
     p, _ = params
     heat, paf = _synth_maps(config, TWO_PEOPLE)

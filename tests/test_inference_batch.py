@@ -1,6 +1,7 @@
-"""Batched inference on the CPU: composed resample tables, predict_batch /
-process_batch against their per-image counterparts, batched post-processing,
-and the batch endpoints of the service."""
+"""Inference pipeline on the CPU: composed resample tables, predict /
+predict_batch against the per-image torch-chain oracle, process_batch and the
+batched post-processing against their per-image wrappers (grouping, chunking,
+per-image offsets), and the batch endpoints of the service."""
 import io
 
 import numpy as np
@@ -15,6 +16,8 @@ from improved_body_parts_amd.engine import (
 from improved_body_parts_amd.models import NetworkEval
 from improved_body_parts_amd.ops.ensemble import (
     TABLE_K, axis_table, compose_axis_matrix, ensemble_merge, table_to_matrix)
+
+from inference_oracle import reference_predict
 
 
 @pytest.fixture(scope="module")
@@ -104,7 +107,7 @@ def test_ensemble_merge_cpu_writes_and_accumulates():
 
 
 # --------------------------------------------------------------------------
-# predict_batch against predict
+# predict and predict_batch against the per-image torch chain
 # --------------------------------------------------------------------------
 
 def _three_images():
@@ -120,15 +123,46 @@ def _check_predict_batch(model, config, p, mp, atol):
     assert len(got) == 3
     worst = 0.0
     for img, (heat, paf) in zip(imgs, got):
-        h_ref, p_ref = predict(img, model, config, p, mp)
+        h_ref, p_ref = reference_predict(img, model, config, p, mp)
         assert heat.shape == h_ref.shape and paf.shape == p_ref.shape
         # (H, W, C) views of the planar buffer: the planar permute is free
         assert heat.permute(2, 0, 1).is_contiguous()
         assert paf.permute(2, 0, 1).is_contiguous()
         worst = max(worst, float((heat - h_ref).abs().max()),
                     float((paf - p_ref).abs().max()))
-    print(f"predict_batch vs predict: max abs diff {worst:.3e}")
+    print(f"predict_batch vs torch chain: max abs diff {worst:.3e}")
     assert worst <= atol
+
+
+@pytest.mark.parametrize("hw,boxsize,over", [
+    ((64, 64), 64, {}),
+    ((96, 80), 96, {}),
+    ((96, 80), 120, {"scale_search": [0.8, 1.0]}),
+], ids=["64x64-box64", "96x80-box96", "96x80-box120-two-scales"])
+def test_predict_equals_torch_chain(model, config, hw, boxsize, over):
+    """One image through the batched pipeline: on the CPU the merge is the
+    same eager chain over the same values, so the maps are bit-identical."""
+    p, mp = _params(boxsize, **over)
+    img = np.random.RandomState(4).rand(*hw, 3).astype(np.float32)
+    heat, paf = predict(img, model, config, p, mp)
+    h_ref, p_ref = reference_predict(img, model, config, p, mp)
+    assert heat.dtype == torch.float32 and heat.shape == h_ref.shape
+    assert paf.dtype == torch.float32 and paf.shape == p_ref.shape
+    print(f"predict vs torch chain {hw} box {boxsize}: max abs diff "
+          f"{max(float((heat - h_ref).abs().max()), float((paf - p_ref).abs().max())):.3e}")
+    assert torch.equal(heat, h_ref) and torch.equal(paf, p_ref)
+
+
+def test_predict_rotation_matches_torch_chain(model, config):
+    """A rotated run of one image against the per-image (H, W, C) chain."""
+    p, mp = _params(120, rotation_search=[0.0, 30.0])
+    img = _three_images()[0]
+    heat, paf = predict(img, model, config, p, mp)
+    h_ref, p_ref = reference_predict(img, model, config, p, mp)
+    worst = max(float((heat - h_ref).abs().max()),
+                float((paf - p_ref).abs().max()))
+    print(f"predict (rotated) vs torch chain: max abs diff {worst:.3e}")
+    assert worst <= 1e-4
 
 
 def test_predict_batch_matches_predict(model, config):

@@ -522,19 +522,33 @@ def test_heatmap_nms_matches_util():
     from improved_body_parts_amd.utils import keypoint_heatmap_nms
     torch.manual_seed(0)
     heat = torch.rand(1, 18, 64, 64)
-    got = ops.heatmap_nms(heat.cuda(), 0.1)
-    ref = keypoint_heatmap_nms(heat, 3, 0.1)
-    _assert_close(got, ref, 1e-6, 1e-6)
+    # radius 0: integer coordinates and the peak value itself. The input has
+    # 8436 peaks, so the cap is lifted well over the default 512.
+    buf = _backend.hip_extension().peaks_batched(heat.cuda(), 18, 0.1, 0, 16384)
+    buf = buf.cpu()
+    n = int(buf[0, 0, :1].view(torch.int32))
+    assert n <= 16384
+    rows = buf[0, 1:1 + n]
+    ref = keypoint_heatmap_nms(heat, 3, 0.1)[0]
+    want = ref.nonzero()                                   # (c, y, x) positions
+    assert n == want.shape[0] == 8436
+    got = rows[:, [0, 2, 1]].long()
+    assert torch.equal(got.float(), rows[:, [0, 2, 1]]), "non-integer coordinates"
+    order = np.lexsort((got[:, 2].numpy(), got[:, 1].numpy(), got[:, 0].numpy()))
+    assert torch.equal(got[order], want)                   # zeros elsewhere
+    vals = ref[want[:, 0], want[:, 1], want[:, 2]]
+    assert torch.equal(rows[order, 3], vals) and torch.equal(rows[order, 4], vals)
 
 
 def test_find_peaks_device():
-    from improved_body_parts_amd.ops.postproc import find_peaks_device
     heat = torch.zeros(3, 64, 64)
     heat[0, 10, 20] = 0.9
     heat[2, 40, 30] = 0.8
     # slight spread so centroid refinement has signal
     heat[0, 10, 21] = 0.5
-    peaks = find_peaks_device(heat.cuda(), threshold=0.3, radius=2)
+    buf = _backend.hip_extension().peaks_batched(heat.cuda()[None], 3, 0.3, 2,
+                                                 512).cpu()
+    peaks = buf[0, 1:1 + int(buf[0, 0, :1].view(torch.int32))]
     assert peaks.shape[0] == 2
     rows = {int(r[0]): r for r in peaks}
     assert 0 in rows and 2 in rows
