@@ -16,10 +16,13 @@ MI355X-first design differences from the reference (behavior preserved):
     ``F.interpolate`` / ``grid_sample`` on the GPU instead of cv2 on the host;
     only the final few hundred peak rows ever cross PCIe.
   * Peak NMS + centroid refinement and the O(limbs x nA x nB x 20) limb
-    line-integral scoring run as HIP kernels (ops/csrc/postproc.hip); the host
-    keeps only the tiny greedy assembly over device-scored candidates. This is
-    the fix for the reference's 5.2-FPS pure-Python bottleneck
-    (reference README.md:68).
+    line-integral scoring run as HIP kernels (ops/csrc/postproc.hip,
+    limb_match.hip); the host keeps the greedy matching and assembly over
+    device-scored candidates. This is the fix for the reference's 5.2-FPS
+    pure-Python bottleneck (reference README.md:68). ``matching="device"``
+    (``assign_batch``) also moves candidate enumeration, the acceptance
+    criteria and the greedy 1-1 matching into one kernel, leaving the host
+    ``find_people`` and one synchronisation per batch.
   * Everything falls back to the same torch ops on CPU so the pipeline is
     unit-testable without a GPU.
   * Every stage is written once, for a list of images and a planar
@@ -38,6 +41,8 @@ import torch.nn.functional as F
 
 from ..config import CanonicalConfig, InferenceParams
 from ..ops._backend import use_hip_for, hip_extension
+from ..ops.assignment import (MAX_PEAKS, OVERFLOW, canonical_peaks,
+                              decode_assignment, limb_match)
 from ..ops.ensemble import ensemble_merge
 from ..utils import keypoint_heatmap_nms, refine_centroid
 
@@ -425,6 +430,62 @@ def find_connections(all_peaks, paf_avg, image_height, params, config: Canonical
 
 
 # --------------------------------------------------------------------------
+# assign_batch: peaks -> connections on the device, one host synchronisation
+# --------------------------------------------------------------------------
+
+def _assign_host(maps, params, config, max_peaks=512):
+    """The host-matching path in ``assign_batch``'s return format."""
+    peaks = find_peaks_batch(maps, params, config, max_peaks)
+    conns = find_connections_batch(peaks, maps, params, config)
+    return [(pk, c, sk) for pk, (c, sk) in zip(peaks, conns)]
+
+
+def assign_batch(maps, params, config: CanonicalConfig, max_peaks=512,
+                 max_part=64):
+    """``find_peaks_batch`` + ``find_connections_batch`` of a planar
+    (N, heat + paf, H, W) pipeline buffer with the matching on the device:
+    ``peaks_batched`` -> ``peaks_canonical`` -> ``limb_match`` are queued
+    without a host synchronisation in between, one copy brings peaks, offsets,
+    connection rows and counts back, and numpy decodes them.
+
+    Returns one ``(all_peaks, connection_all, special_k)`` per image. An image
+    in which a part has more than ``max_part`` (<= 64) peaks is redone through
+    the host path, so results are never truncated. On CPU maps the host path
+    runs for every image.
+    """
+    n_parts = config.heat_layers
+    first_limb_plane = config.num_layers - config.paf_layers
+    maps = maps.contiguous().float()
+    if not use_hip_for(maps):
+        return _assign_host(maps, params, config, max_peaks)
+    if max_peaks > MAX_PEAKS:
+        raise ValueError(f"device matching ranks at most {MAX_PEAKS} peaks per "
+                         f"image (max_peaks={max_peaks})")
+    N = maps.shape[0]
+    if N == 0:
+        return []
+    buf = hip_extension().peaks_batched(maps, n_parts, float(params["thre1"]),
+                                        int(params["offset_radius"]), max_peaks)
+    peaks, offsets = canonical_peaks(buf, n_parts)
+    rows, counts = limb_match(maps, peaks, offsets, config.limbs_conn,
+                              first_limb_plane, int(params["mid_num"]),
+                              float(params["thre2"]),
+                              float(params["connect_ration"]), max_part)
+    # one copy, one synchronisation: the int32 tensors travel as fp32 bits
+    parts = (peaks, offsets.view(torch.float32), rows, counts.view(torch.float32))
+    flat = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy()
+    host, lo = [], 0
+    for t in parts:
+        host.append(flat[lo:lo + t.numel()].reshape(t.shape))
+        lo += t.numel()
+    counts_np = host[3].view(np.int32)
+    out = decode_assignment(host[0], host[1].view(np.int32), host[2], counts_np)
+    for n in np.nonzero((counts_np == OVERFLOW).any(axis=1))[0]:
+        out[n] = _assign_host(maps[n:n + 1], params, config, max_peaks)[0]
+    return out
+
+
+# --------------------------------------------------------------------------
 # find_people: greedy subset assembly (host — tiny)
 # --------------------------------------------------------------------------
 
@@ -582,27 +643,33 @@ def subsets_to_keypoints(subset, candidate, config: CanonicalConfig):
 
 @torch.no_grad()
 def process_batch(images, model, config: CanonicalConfig, params=None,
-                  model_params=None, max_views=16):
+                  model_params=None, max_views=16, matching="host"):
     """Full pipeline for a list of images (reference evaluate.py:500-542):
     batched forward and ensemble merge, batched peak and limb kernels, then the
-    per-image greedy assembly. Returns one list of (coco_keypoints, score) per
-    image, in input order."""
+    per-image greedy assembly. ``matching="host"`` scores limb candidates on
+    the device and matches them on the host; ``"device"`` does both in
+    ``assign_batch``. Returns one list of (coco_keypoints, score) per image, in
+    input order."""
+    if matching not in ("host", "device"):
+        raise ValueError(f"matching must be 'host' or 'device', got {matching!r}")
     params, model_params = _resolve_params(params, model_params)
     results = [None] * len(images)
     for idxs, maps in _predict_groups(images, model, config, params,
                                       model_params, max_views):
-        peaks = find_peaks_batch(maps, params, config)
-        conns = find_connections_batch(peaks, maps, params, config)
-        for i, all_peaks, (connection_all, special_k) in zip(idxs, peaks, conns):
+        assign = assign_batch if matching == "device" else _assign_host
+        assigned = assign(maps, params, config)
+        for i, (all_peaks, connection_all, special_k) in zip(idxs, assigned):
             subset, candidate = find_people(connection_all, special_k, all_peaks,
                                             params, config)
             results[i] = subsets_to_keypoints(subset, candidate, config)
     return results
 
 
-def process(image, model, config: CanonicalConfig, params=None, model_params=None):
+def process(image, model, config: CanonicalConfig, params=None, model_params=None,
+            matching="host"):
     """``process_batch`` for one image -> list of (coco_keypoints, score)."""
-    return process_batch([image], model, config, params, model_params)[0]
+    return process_batch([image], model, config, params, model_params,
+                         matching=matching)[0]
 
 
 def format_results(keypoints, res_file):

@@ -101,10 +101,18 @@ Tensor heatmap_gt(const Tensor& joints, const c10::optional<Tensor>& mask_all,
                   double keypoint_thre, double limb_thre, double paf_thre);
 
 // postproc.hip
-Tensor limb_scores(const Tensor& paf, const Tensor& peaks, const Tensor& cand_idx,
-                   int64_t mid_num, double thre2);
 Tensor peaks_batched(const Tensor& maps, int64_t heat_layers, double thre,
                      int64_t radius, int64_t max_peaks);
+
+// limb_match.hip
+Tensor limb_scores(const Tensor& paf, const Tensor& peaks, const Tensor& cand_idx,
+                   int64_t mid_num, double thre2);
+std::vector<Tensor> peaks_canonical(const Tensor& buf, int64_t n_parts);
+std::vector<Tensor> limb_match(const Tensor& maps, const Tensor& peaks,
+                               const Tensor& offsets, const Tensor& limbs,
+                               int64_t first_limb_plane, int64_t mid_num,
+                               double thre2, double connect_ration,
+                               int64_t max_part);
 
 // ensemble_merge.hip
 void ensemble_merge(const Tensor& src, const Tensor& chan_main,
@@ -168,6 +176,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("paf_sigma"), py::arg("keypoint_thre"), py::arg("limb_thre"),
         py::arg("paf_thre"));
   m.def("limb_scores", &limb_scores);
+  m.def("peaks_canonical", &peaks_canonical,
+        "peaks_batched buffer -> rows in (channel, y, x) order + channel offsets",
+        py::arg("buf"), py::arg("n_parts"));
+  m.def("limb_match", &limb_match,
+        "per (image, limb): score, filter and greedily match all nA x nB segments",
+        py::arg("maps"), py::arg("peaks"), py::arg("offsets"), py::arg("limbs"),
+        py::arg("first_limb_plane"), py::arg("mid_num"), py::arg("thre2"),
+        py::arg("connect_ration"), py::arg("max_part"));
   m.def("peaks_batched", &peaks_batched,
         "fused NMS + centroid refinement over a planar batch, per-image counters",
         py::arg("maps"), py::arg("heat_layers"), py::arg("thre"),

@@ -1,10 +1,10 @@
 // On-device keypoint post-processing primitives.
 //
 // Replaces the reference's CPU-bound post-process stages (5.2 FPS headline
-// bottleneck, reference README.md:68): peak NMS (utils/util.py:177-183),
-// sub-pixel centroid refinement (:186-211) and the 20-point limb line-integral
-// scoring of find_connections (evaluate.py:206-276). The tiny greedy assembly
-// stays on the host, consuming the device-scored candidates.
+// bottleneck, reference README.md:68): peak NMS (utils/util.py:177-183) and
+// sub-pixel centroid refinement (:186-211). The 20-point limb line-integral
+// scoring of find_connections (evaluate.py:206-276) and the device-side
+// matching are in limb_match.hip.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
@@ -72,50 +72,6 @@ __global__ void peaks_batched_kernel(const float* __restrict__ maps,
   }
 }
 
-// Score every candidate limb: sample mid_num points along each A->B segment on
-// the limb channel; emit [mean_score_with_dist_prior, pass_ratio, length].
-// grid: one thread per (limb_type, a, b) candidate triple (flattened).
-template <typename T>
-__global__ void limb_score_kernel(
-    const T* __restrict__ paf,          // [Cpaf, H, W]
-    const float* __restrict__ peaks,    // [P][5] rows as peaks_batched writes
-    const int* __restrict__ cand_idx,   // [ncand][3]: limb_id, peakA, peakB
-    float* __restrict__ scores,         // [ncand][3]
-    int ncand, int H, int W, int mid_num, float thre2) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < ncand;
-       i += gridDim.x * blockDim.x) {
-    int limb = cand_idx[i * 3 + 0];
-    const float* pa = peaks + (long long)cand_idx[i * 3 + 1] * 5;
-    const float* pb = peaks + (long long)cand_idx[i * 3 + 2] * 5;
-    float ax = pa[1], ay = pa[2], bx = pb[1], by = pb[2];
-    float dx = bx - ax, dy = by - ay;
-    float len = sqrtf(dx * dx + dy * dy) + 1e-9f;
-    const T* plane = paf + (long long)limb * H * W;
-    float sum = 0.f;
-    int pass = 0;
-    // short limbs sample fewer points (reference evaluate.py:228:
-    // mid_num = min(round(norm)+1, param mid_num))
-    const int mn = min((int)roundf(len) + 1, mid_num);
-    for (int k = 0; k < mn; ++k) {
-      float t = mn == 1 ? 0.f : (float)k / (mn - 1);
-      int x = (int)roundf(ax + t * dx);
-      int y = (int)roundf(ay + t * dy);
-      x = min(max(x, 0), W - 1);
-      y = min(max(y, 0), H - 1);
-      float v = ldf(plane + (long long)y * W + x);
-      sum += v;
-      if (v > thre2) ++pass;
-    }
-    float mean = sum / mn;
-    // distance prior of the reference (evaluate.py:240): penalise limbs longer
-    // than half the image height
-    float prior = fminf(0.5f * H / len - 1.f, 0.f);
-    scores[i * 3 + 0] = mean + prior;
-    scores[i * 3 + 1] = (float)pass / mn;
-    scores[i * 3 + 2] = len;
-  }
-}
-
 }  // namespace ibp
 
 using torch::Tensor;
@@ -144,24 +100,4 @@ Tensor peaks_batched(const Tensor& maps, int64_t heat_layers, double thre,
                      (int)heat_layers, P, H, W, (float)thre, (int)radius,
                      (int)max_peaks);
   return out;
-}
-
-Tensor limb_scores(const Tensor& paf, const Tensor& peaks, const Tensor& cand_idx,
-                   int64_t mid_num, double thre2) {
-  int W = (int)paf.size(-1), H = (int)paf.size(-2);
-  int ncand = (int)cand_idx.size(0);
-  Tensor scores = torch::zeros({std::max(ncand, 1), 3},
-                               paf.options().dtype(torch::kFloat32));
-  if (ncand == 0) return scores;
-  dim3 block(256), grid(ibp::grid_1d(ncand, 256, 2048));
-  AT_DISPATCH_FLOATING_TYPES_AND2(at::ScalarType::BFloat16, at::ScalarType::Half,
-      paf.scalar_type(), "limb_scores", [&] {
-    hipLaunchKernelGGL(ibp::limb_score_kernel<scalar_t>, grid, block, 0,
-                       cur_stream4(),
-                       reinterpret_cast<const scalar_t*>(paf.data_ptr()),
-                       peaks.data_ptr<float>(), cand_idx.data_ptr<int>(),
-                       scores.data_ptr<float>(), ncand, H, W, (int)mid_num,
-                       (float)thre2);
-  });
-  return scores;
 }

@@ -41,7 +41,11 @@ class PoseService:
 
     def __init__(self, config_name: str = "Canonical", nstack: int = 4,
                  checkpoint: Optional[str] = None, device: Optional[str] = None,
-                 bf16: Optional[bool] = None):
+                 bf16: Optional[bool] = None, matching: str = "host"):
+        if matching not in ("host", "device"):
+            raise ValueError(
+                f"matching must be 'host' or 'device', got {matching!r}")
+        self.matching = matching
         self.config = GetConfig(config_name)
         self.opt = TrainingOpt(nstack=nstack, batch_size=1)
         self.device = torch.device(device or
@@ -69,7 +73,7 @@ class PoseService:
         """image (H, W, 3) float32 in [0,1] -> list of people dicts."""
         with self._lock, torch.no_grad():
             people = process(image, self.model, self.config, self.params,
-                             self.model_params)
+                             self.model_params, matching=self.matching)
         return self._people_dicts(people)
 
     def infer_many(self, images):
@@ -77,7 +81,8 @@ class PoseService:
         one list of people dicts per image, via the batched pipeline."""
         with self._lock, torch.no_grad():
             batch = process_batch(list(images), self.model, self.config,
-                                  self.params, self.model_params)
+                                  self.params, self.model_params,
+                                  matching=self.matching)
         return [self._people_dicts(people) for people in batch]
 
     @staticmethod

@@ -19,6 +19,10 @@ ap.add_argument("--batch", type=int, nargs="+", default=[1],
                      "Several values are measured in turn on the same model")
 ap.add_argument("--images", type=int, default=24, help="images per timed pass")
 ap.add_argument("--repeats", type=int, default=1, help="timed passes per --batch")
+ap.add_argument("--matching", choices=["host", "device"], nargs="+",
+                default=["host"],
+                help="where limb candidates are matched; several values "
+                     "alternate inside each repeat on the same model")
 args = ap.parse_args()
 
 config = GetConfig("Canonical")
@@ -65,18 +69,19 @@ ds = SyntheticPoseDataset(config, length=64, render=True, seed=3)
 imgs = [ds.generate(i % 64)[0] for i in range(args.images)]
 
 
-def measure(batch_size):
+def measure(batch_size, matching):
     """Warm up, then time one pass over ``imgs``; returns (img/s, people)."""
     if batch_size > 1:
         def run(batch):
-            return sum(len(r) for r in process_batch(batch, model, config, p, mp))
+            return sum(len(r) for r in process_batch(batch, model, config, p, mp,
+                                                     matching=matching))
         chunks = [imgs[i:i + batch_size] for i in range(0, len(imgs), batch_size)]
         # warm every batch size the timed loop uses
         for n in sorted({len(c) for c in chunks}):
             run(imgs[:n])
     else:
         def run(batch):
-            return len(process(batch[0], model, config, p, mp))
+            return len(process(batch[0], model, config, p, mp, matching=matching))
         chunks = [[img] for img in imgs]
         for img in imgs[:4]:
             run([img])                               # warmup
@@ -91,9 +96,11 @@ def measure(batch_size):
 # several --batch values alternate inside each repeat, so they see the same
 # machine state and their spread can be compared
 for rep in range(args.repeats):
-    for b in args.batch:
-        fps, n_people = measure(b)
+    for b, matching in ((b, m) for b in args.batch for m in args.matching):
+        fps, n_people = measure(b, matching)
         label = f"process_batch(batch={b})" if b > 1 else "process()"
+        if matching != "host":
+            label = label[:-1] + (", " if b > 1 else "") + f"matching={matching})"
         print(f"end-to-end {label} {fps:.1f} img/s over {len(imgs)} images "
               f"({n_people} people found; 512^2, {opt.nstack}-stack, single scale, "
               f"flip ensemble, {'trained ' + str(args.train_steps) + ' steps' if args.train_steps else 'random-init'})",
