@@ -4,6 +4,7 @@
 using torch::Tensor;
 
 // bn_act.hip
+std::vector<int64_t> bn_v8_geometry(int64_t M, int64_t C);
 std::vector<Tensor> bn_stats(const Tensor& x_mc, int64_t C);
 std::vector<Tensor> bn_finalize(
     const Tensor& sums, const Tensor& sumsq, int64_t M, const Tensor& gamma,
@@ -122,6 +123,9 @@ void ensemble_merge(const Tensor& src, const Tensor& chan_main,
                     int64_t wr, int64_t wc, int64_t span);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("bn_v8_geometry", &bn_v8_geometry,
+        "debug: [cpb, rpb, rows, grid_y] of the bf16 v8 stats/reduce launch",
+        py::arg("M"), py::arg("C"));
   m.def("bn_stats", &bn_stats, "per-channel sum/sumsq of an [M][C] view");
   m.def("bn_finalize", &bn_finalize,
         "mean/invstd/scale/shift epilogue over given (possibly all-reduced) sums");

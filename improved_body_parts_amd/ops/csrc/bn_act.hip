@@ -515,6 +515,15 @@ static inline void v8_geometry(long long M, int C8, int& cpb, int& rpb,
   rows = std::max(rows, 1);
 }
 
+// debug: the launch geometry the bf16 v8 kernels use for an [M][C] view,
+// as [cpb, rpb, rows, grid_y] (tests pin the cases they mean to cover)
+std::vector<int64_t> bn_v8_geometry(int64_t M, int64_t C) {
+  TORCH_CHECK(M > 0 && C > 0 && C % 8 == 0, "bn_v8_geometry: C % 8 == 0");
+  int C8 = (int)C / 8, cpb, rpb, rows;
+  v8_geometry(M, C8, cpb, rpb, rows);
+  return {cpb, rpb, rows, (C8 + cpb - 1) / cpb};
+}
+
 std::vector<Tensor> bn_stats(const Tensor& x_mc, int64_t C) {
   TORCH_CHECK(x_mc.is_cuda() && dense_ok(x_mc));
   long long M = x_mc.numel() / C;
