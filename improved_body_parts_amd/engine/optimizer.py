@@ -46,7 +46,17 @@ class FusedSGD(Optimizer):
                 buf = state["momentum_buffer"]
                 master = state.get("master")
                 if p.is_cuda and hip_available():
-                    hip_batch.append((p, p.grad, buf, master))
+                    from ..ops.optim import same_layout
+                    g = p.grad
+                    if not same_layout(g, p):
+                        # the kernel pairs param/grad/momentum/master by
+                        # linear memory offset: a gradient in another memory
+                        # format (set by hand, or by a path that skips
+                        # AccumulateGrad's layout contract) is brought into
+                        # the parameter's layout first
+                        g = torch.empty_like(
+                            p, memory_format=torch.preserve_format).copy_(g)
+                    hip_batch.append((p, g, buf, master))
                     continue
                 # eager path (CPU oracle / debugging)
                 w = master if master is not None else p

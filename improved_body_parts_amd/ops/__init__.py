@@ -200,6 +200,11 @@ def focal_l2_loss(pred, gt, mask, *, heat_start, bkg_start, gamma=1,
             m = F.interpolate(mask.float(), size=(h, w), mode="bilinear",
                               align_corners=False)
             mask = ((m >= 0.5).float() * m).to(pred.dtype)
+        # the kernels read gt and mask with pred's element type
+        if gt.dtype != pred.dtype:
+            gt = gt.to(pred.dtype)
+        if mask.dtype != pred.dtype:
+            mask = mask.to(pred.dtype)
         return _loss.focal_l2_loss_hip(pred, gt, mask, heat_start=heat_start,
                                        bkg_start=bkg_start, gamma=gamma,
                                        multi_task_weight=multi_task_weight,

@@ -88,6 +88,8 @@ Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
                        int64_t W, int64_t Cin, int64_t Cout, int64_t KH,
                        int64_t KW, int64_t stride, int64_t pad_h, int64_t pad_w,
                        int64_t dil_h, int64_t dil_w, int64_t Ho, int64_t Wo);
+std::vector<int64_t> conv_wgrad_plan(int64_t M, int64_t Cin, int64_t Cout,
+                                     int64_t KH, int64_t KW);
 Tensor tr16_probe();
 
 // sgd.hip
@@ -170,6 +172,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("fwd_pack"), py::arg("dgrad_pack") = c10::nullopt);
   m.def("conv_mfma_wgrad", &conv_mfma_wgrad,
         "MFMA implicit-GEMM conv weight gradient (tr16 LDS transpose)");
+  m.def("conv_wgrad_plan", &conv_wgrad_plan,
+        "debug: [TKD, TCO, waves, elem, kd_cb, chunks, chunk_len, tree group "
+        "counts...] planned for a weight gradient with M = N*Ho*Wo",
+        py::arg("M"), py::arg("Cin"), py::arg("Cout"), py::arg("KH"),
+        py::arg("KW"));
   m.def("tr16_probe", &tr16_probe,
         "debug: ds_read_b64_tr_b16 delivery-map probe");
   m.def("fused_sgd", &fused_sgd);

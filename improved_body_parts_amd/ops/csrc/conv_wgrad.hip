@@ -439,6 +439,82 @@ __global__ void tr16_probe_kernel(short* out) {
 // ===========================================================================
 using torch::Tensor;
 
+// Every host decision of one wgrad launch. conv_mfma_wgrad launches from it
+// and conv_wgrad_plan exposes it, so the tests pin exactly what runs.
+struct WgradPlan {
+  int TKD, TCO, nwaves;
+  bool big, wide, mid, elem;
+  int kd_tiles, co_tiles, kd_cb, chunks;
+  long long chunk_len;             // multiple of 64
+  std::vector<int> tree_groups;    // group count of each tree-reduce stage
+};
+
+static WgradPlan plan_wgrad(long long M, int64_t Cin, int64_t Cout, int64_t KH,
+                            int64_t KW) {
+  WgradPlan pl;
+  const int KD = (int)(KH * KW * Cin);
+  // Tile selection. The wide-spatial 3x3 layers are L3-BANDWIDTH-bound on
+  // re-reads: with a TCOxTKD grid each x byte is read (taps * Cout/TCO)
+  // times and each dy byte (KD/TKD) times per chunk (~9.7 GB for the
+  // 256ch@128^2 layer at 64x64 — about the measured runtime at L3 rate).
+  // TCO=128 halves both factors; TKD stays 64 (128x128 at 2 blocks/CU
+  // measured slower — latency). Small-M layers keep 64x64 (fit in L2, and
+  // the 12-subtile LDS drops occupancy 4 -> 3).
+  const char* bt = getenv("IBP_WGRAD_BIG");
+  pl.big = bt && bt[0] == '1' && KD >= 128 && Cout >= 128;
+  // wide tile measured: 1x1 @128^2 0.78 -> 0.87x MIOpen, but 3x3 0.60 ->
+  // 0.37x (the occupancy-3->2 latency cost beats the halved re-reads when
+  // the tap factor, not Cout/TCO, dominates traffic) -> 1x1 only
+  pl.wide = !pl.big && KH == 1 && KW == 1 && Cout >= 128 && M >= 65536;
+  // mid tile (128x128 @ 8 waves): for the LDS-read-bound wide-spatial KxK
+  // layers — same waves/SIMD as 64x64 but 25% fewer tr-read bytes per FLOP
+  pl.mid = !pl.big && !pl.wide && KH * KW > 1 && KD >= 1024 &&
+           Cout >= 128 && M >= 65536;
+  pl.TKD = (pl.big || pl.mid) ? 128 : 64;
+  pl.TCO = (pl.big || pl.mid || pl.wide) ? 128 : 64;
+  pl.nwaves = pl.mid ? 8 : 4;
+  pl.kd_tiles = (KD + pl.TKD - 1) / pl.TKD;
+  pl.co_tiles = (int)((Cout + pl.TCO - 1) / pl.TCO);
+  pl.kd_cb = 0;
+  if (KH * KW > 1 && Cin % pl.TKD == 0) pl.kd_cb = (int)(Cin / pl.TKD);
+  if (const char* e = getenv("IBP_WGRAD_NOREORDER"))
+    if (e[0] == '1') pl.kd_cb = 0;
+  // split M into chunks for parallelism: aim ~768 blocks, chunk length a
+  // multiple of 64; every chunk slice is fully written (plain stores) before
+  // the combine reduces them in fixed order -> deterministic
+  const int tiles = pl.kd_tiles * pl.co_tiles;
+  // r14 sweep on (256ch, 3x3, 128^2): 768 blocks -> 0.758 ms, 3072 -> 0.712,
+  // 6144 -> 0.691 — more chunks win there (load balance). But a chunk must
+  // still run >= ~32 pipeline stages or the block is pure prologue (r15: the
+  // unconditional 6144 target dropped 1-stage chunks to 0.28-0.48x) — cap
+  // chunks so every block keeps >= 32 x 64-m stages.
+  long long max_chunks = std::max<long long>(M / (64 * 32), 1);
+  int target_blocks = 6144;
+  if (const char* e = getenv("IBP_WGRAD_BLOCKS")) target_blocks = atoi(e);
+  long long want = (target_blocks + tiles - 1) / tiles;
+  long long chunks = std::min<long long>(std::max<long long>(want, 1), max_chunks);
+  pl.chunk_len = (((M + chunks - 1) / chunks + 63) / 64) * 64;
+  pl.chunks = (int)((M + pl.chunk_len - 1) / pl.chunk_len);
+  // tap-crossing pieces exist iff Cin is not 16-aligned or the last kd-tile
+  // is partial — only then compile in the per-element path (costs VGPRs)
+  pl.elem = (Cin % 16 != 0) || (KD % pl.TKD != 0);
+  // tree stages (groups of 8) until the final scatter loops over <= 16 slices
+  for (int left = pl.chunks; left > 16;) {
+    left = (left + 7) / 8;
+    pl.tree_groups.push_back(left);
+  }
+  return pl;
+}
+
+std::vector<int64_t> conv_wgrad_plan(int64_t M, int64_t Cin, int64_t Cout,
+                                     int64_t KH, int64_t KW) {
+  const WgradPlan pl = plan_wgrad(M, Cin, Cout, KH, KW);
+  std::vector<int64_t> out = {pl.TKD, pl.TCO, pl.nwaves, pl.elem ? 1 : 0,
+                              pl.kd_cb, pl.chunks, pl.chunk_len};
+  for (int g : pl.tree_groups) out.push_back(g);
+  return out;
+}
+
 Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
                        int64_t W, int64_t Cin, int64_t Cout, int64_t KH,
                        int64_t KW, int64_t stride, int64_t pad_h, int64_t pad_w,
@@ -456,48 +532,14 @@ Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
   p.KD = (int)(KH * KW * Cin);
   p.step_dho = 64 / p.Wo;
   p.step_dwo = 64 % p.Wo;
-  p.kd_cb = 0;  // set below once TKD is chosen
-  // Tile selection. The wide-spatial 3x3 layers are L3-BANDWIDTH-bound on
-  // re-reads: with a TCOxTKD grid each x byte is read (taps * Cout/TCO)
-  // times and each dy byte (KD/TKD) times per chunk (~9.7 GB for the
-  // 256ch@128^2 layer at 64x64 — about the measured runtime at L3 rate).
-  // TCO=128 halves both factors; TKD stays 64 (128x128 at 2 blocks/CU
-  // measured slower — latency). Small-M layers keep 64x64 (fit in L2, and
-  // the 12-subtile LDS drops occupancy 4 -> 3).
-  const char* bt = getenv("IBP_WGRAD_BIG");
-  const bool big = bt && bt[0] == '1' && p.KD >= 128 && Cout >= 128;
-  // wide tile measured: 1x1 @128^2 0.78 -> 0.87x MIOpen, but 3x3 0.60 ->
-  // 0.37x (the occupancy-3->2 latency cost beats the halved re-reads when
-  // the tap factor, not Cout/TCO, dominates traffic) -> 1x1 only
-  const bool wide = !big && KH == 1 && KW == 1 && Cout >= 128 &&
-                    p.M >= 65536;
-  // mid tile (128x128 @ 8 waves): for the LDS-read-bound wide-spatial KxK
-  // layers — same waves/SIMD as 64x64 but 25% fewer tr-read bytes per FLOP
-  const bool mid = !big && !wide && KH * KW > 1 && p.KD >= 1024 &&
-                   Cout >= 128 && p.M >= 65536;
-  const int TKD = (big || mid) ? 128 : 64;
-  const int TCO = (big || mid || wide) ? 128 : 64;
-  p.kd_tiles = (p.KD + TKD - 1) / TKD;
-  p.co_tiles = (int)((Cout + TCO - 1) / TCO);
-  if (KH * KW > 1 && Cin % TKD == 0) p.kd_cb = (int)(Cin / TKD);
-  if (const char* e = getenv("IBP_WGRAD_NOREORDER"))
-    if (e[0] == '1') p.kd_cb = 0;
-  // split M into chunks for parallelism: aim ~768 blocks, chunk length a
-  // multiple of 64; every chunk slice is fully written (plain stores) before
-  // the combine reduces them in fixed order -> deterministic
+  const WgradPlan pl = plan_wgrad(p.M, Cin, Cout, KH, KW);
+  const bool big = pl.big, wide = pl.wide, mid = pl.mid, elem = pl.elem;
+  p.kd_tiles = pl.kd_tiles;
+  p.co_tiles = pl.co_tiles;
+  p.kd_cb = pl.kd_cb;
+  p.chunk_len = pl.chunk_len;
+  p.chunks = pl.chunks;
   const int tiles = p.kd_tiles * p.co_tiles;
-  // r14 sweep on (256ch, 3x3, 128^2): 768 blocks -> 0.758 ms, 3072 -> 0.712,
-  // 6144 -> 0.691 — more chunks win there (load balance). But a chunk must
-  // still run >= ~32 pipeline stages or the block is pure prologue (r15: the
-  // unconditional 6144 target dropped 1-stage chunks to 0.28-0.48x) — cap
-  // chunks so every block keeps >= 32 x 64-m stages.
-  long long max_chunks = std::max<long long>(p.M / (64 * 32), 1);
-  int target_blocks = 6144;
-  if (const char* e = getenv("IBP_WGRAD_BLOCKS")) target_blocks = atoi(e);
-  long long want = (target_blocks + tiles - 1) / tiles;
-  long long chunks = std::min<long long>(std::max<long long>(want, 1), max_chunks);
-  p.chunk_len = (((p.M + chunks - 1) / chunks + 63) / 64) * 64;
-  p.chunks = (int)((p.M + p.chunk_len - 1) / p.chunk_len);
 
   auto stream = at::hip::getCurrentHIPStream().stream();
   Tensor ws = torch::empty({(long long)p.chunks * p.KD * Cout},
@@ -506,9 +548,6 @@ Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
   // every in-range (kd, cout) is written by exactly one block per chunk;
   // out-of-range rows are never read back -> no zero-init needed
   dim3 grid(p.chunks * tiles), block(256);
-  // tap-crossing pieces exist iff Cin is not 16-aligned or the last kd-tile
-  // is partial — only then compile in the per-element path (costs VGPRs)
-  const bool elem = (Cin % 16 != 0) || (p.KD % TKD != 0);
   if (mid && elem) {
     hipLaunchKernelGGL((ibp::conv_wgrad_kernel<128, 128, true, 8>), grid,
                        dim3(512), 0, stream, p);
@@ -540,10 +579,9 @@ Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
   const float* ws_ptr = p.ws;
   int chunks_left = p.chunks;
   Tensor partial;
-  while (chunks_left > 16) {
+  for (const int groups : pl.tree_groups) {
     // tree stages until the final scatter loops over <= 16 slices
     const int G = 8;
-    const int groups = (chunks_left + G - 1) / G;
     const long long per_chunk = (long long)p.KD * Cout;
     Tensor next = torch::empty({(long long)groups * per_chunk},
                                x.options().dtype(torch::kFloat32));

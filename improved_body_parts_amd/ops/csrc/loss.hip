@@ -29,6 +29,18 @@ __device__ __forceinline__ float chan_weight(int c, int C, int heat_start,
   return 1.0f;
 }
 
+// u = 1 - st, the base of the focal factor, without the round trip through
+// st: on the negative branch 1 - (1 - s - beta) cancels, which leaves u with
+// an ABSOLUTE error of 2^-25 — a relative one of 2^-25 / (s + beta), several
+// fp32 ulps for small s — and that error is cubed into the gamma = 2
+// gradient. s + beta and (1 - s) + alpha round once, relative to u itself.
+// With alpha = beta = 0 the positive branch is bit-identical to 1 - st and the
+// negative one differs only where 1 - s is inexact (|s| below 2^-15 in bf16).
+__device__ __forceinline__ float focal_base(bool pos, float s, float alpha,
+                                            float beta) {
+  return pos ? (1.f - s) + alpha : s + beta;
+}
+
 // average of the r x r full-res window backing low-res pixel (y, x)
 // (== adaptive_avg_pool2d with an integer ratio)
 template <typename T>
@@ -94,8 +106,7 @@ __global__ void focal_l2_fwd_kernel(
     float sv = ldf(p + i);
     float gv = gt_window_avg(gt + nc * HW0, W0, y, x, r);
     float mv = mask_bilinear_thr(mask + (long long)n * HW0, H0, W0, y, x, r);
-    float st = gv >= 0.01f ? sv - alpha : 1.f - sv - beta;
-    float u = 1.f - st;
+    float u = focal_base(gv >= 0.01f, sv, alpha, beta);
     float factor = GAMMA == 1 ? fabsf(u) : u * u;
     float d = sv - gv;
     acc += d * d * factor * mv * chan_weight(c, C, heat_start, bkg_start, mtw, ktw);
@@ -129,14 +140,13 @@ __global__ void focal_l2_bwd_kernel(
     float gv = gt_window_avg(gt + nc * HW0, W0, y, x, r);
     float mv = mask_bilinear_thr(mask + (long long)n * HW0, H0, W0, y, x, r);
     bool pos = gv >= 0.01f;
-    float st = pos ? sv - alpha : 1.f - sv - beta;
-    float u = 1.f - st;
+    float u = focal_base(pos, sv, alpha, beta);
     float d = sv - gv;
     float factor, dfactor_ds;
     if (GAMMA == 1) {
       factor = fabsf(u);
       float sgn = u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f);
-      // du/ds = -dst/ds ; dst/ds = pos ? 1 : -1
+      // du/ds = pos ? -1 : 1
       dfactor_ds = sgn * (pos ? -1.f : 1.f);
     } else {
       factor = u * u;
@@ -164,13 +174,39 @@ static int pyramid_ratio(const Tensor& pred, const Tensor& gt) {
   return H0 / H;
 }
 
+// The kernels read gt and mask through pointers of pred's element type and
+// index them as [N][C][H0][W0] / [N][1][H0][W0]: a dtype or shape mismatch
+// would read garbage or run past the end of a buffer, so it is an error here.
+static void check_focal_inputs(const Tensor& pred, const Tensor& gt,
+                               const Tensor& mask) {
+  TORCH_CHECK(pred.is_cuda() && gt.is_cuda() && mask.is_cuda() &&
+                  gt.device() == pred.device() &&
+                  mask.device() == pred.device(),
+              "focal_l2: pred, gt and mask must live on one GPU");
+  TORCH_CHECK(pred.dim() == 5 && pred.is_contiguous(),
+              "focal_l2: pred must be a contiguous [S, N, C, H, W] tensor");
+  TORCH_CHECK(gt.scalar_type() == pred.scalar_type() &&
+                  mask.scalar_type() == pred.scalar_type(),
+              "focal_l2: gt (", gt.scalar_type(), ") and mask (",
+              mask.scalar_type(), ") must have pred's dtype (",
+              pred.scalar_type(), ")");
+  TORCH_CHECK(gt.dim() == 4 && gt.is_contiguous() &&
+                  gt.size(0) == pred.size(1) && gt.size(1) == pred.size(2),
+              "focal_l2: gt must be a contiguous [N, C, H0, W0] tensor "
+              "matching pred's N and C");
+  TORCH_CHECK(mask.dim() == 4 && mask.is_contiguous() &&
+                  mask.size(0) == pred.size(1) && mask.size(1) == 1 &&
+                  mask.size(2) == gt.size(2) && mask.size(3) == gt.size(3),
+              "focal_l2: mask must be a contiguous [N, 1, H0, W0] tensor at "
+              "gt's resolution");
+}
+
 // returns per-stack sums [S] (fp32); host applies nstack weights.
 // gt/mask may be FULL resolution: the kernel pools/samples on the fly.
 Tensor focal_l2_fwd(const Tensor& pred, const Tensor& gt, const Tensor& mask,
                     int64_t heat_start, int64_t bkg_start, int64_t gamma,
                     double mtw, double ktw, double alpha, double beta) {
-  TORCH_CHECK(pred.dim() == 5 && pred.is_contiguous());
-  TORCH_CHECK(gt.is_contiguous() && mask.is_contiguous());
+  check_focal_inputs(pred, gt, mask);
   int S = (int)pred.size(0), N = (int)pred.size(1), C = (int)pred.size(2);
   int H = (int)pred.size(3), W = (int)pred.size(4);
   int H0 = (int)gt.size(2), W0 = (int)gt.size(3);
@@ -202,6 +238,12 @@ Tensor focal_l2_bwd(const Tensor& pred, const Tensor& gt, const Tensor& mask,
                     const Tensor& stack_gscale, int64_t heat_start,
                     int64_t bkg_start, int64_t gamma, double mtw, double ktw,
                     double alpha, double beta) {
+  check_focal_inputs(pred, gt, mask);
+  TORCH_CHECK(stack_gscale.is_cuda() &&
+                  stack_gscale.scalar_type() == at::ScalarType::Float &&
+                  stack_gscale.is_contiguous() &&
+                  stack_gscale.numel() == pred.size(0),
+              "focal_l2_bwd: stack_gscale must be a contiguous fp32 [S] tensor");
   int S = (int)pred.size(0), N = (int)pred.size(1), C = (int)pred.size(2);
   int H = (int)pred.size(3), W = (int)pred.size(4);
   int H0 = (int)gt.size(2), W0 = (int)gt.size(3);

@@ -9,9 +9,53 @@ CHUNK = 1 << 16
 _table_cache = {}
 
 
+def _dense(t):
+    """True when ``t`` covers numel() distinct consecutive elements of memory
+    (any dimension order, no gaps, no overlap)."""
+    dims = sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz != 1)
+    expect = 1
+    for st, sz in dims:
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def same_layout(a, b):
+    """Same shape and the same strides on every dimension longer than 1 (the
+    stride of a length-1 dimension addresses nothing)."""
+    return a.shape == b.shape and all(
+        sa == sb for sa, sb, sz in zip(a.stride(), b.stride(), a.shape)
+        if sz != 1)
+
+
+def _check_row(i, p, g, m, master):
+    """The kernel pairs the tensors of a row by linear memory offset: that is
+    the same logical element only if all of them are dense with the strides
+    of the parameter. Runs when a table is built, never on a cached step."""
+    if p.dtype not in (torch.bfloat16, torch.float32) or \
+            g.dtype != p.dtype or m.dtype != torch.float32 or \
+            (master is not None and master.dtype != torch.float32):
+        raise ValueError(
+            f"fused_sgd_step: row {i}: the parameter must be bf16 or fp32 "
+            f"(is {p.dtype}), the grad of the same dtype (is {g.dtype}), "
+            f"momentum and master fp32")
+    for name, t in (("param", p), ("grad", g), ("momentum", m),
+                    ("master", master)):
+        if t is None:
+            continue
+        if t.shape != p.shape or not same_layout(t, p) or not _dense(t):
+            raise ValueError(
+                f"fused_sgd_step: row {i}: {name} has shape {tuple(t.shape)} "
+                f"strides {t.stride()}, parameter has shape {tuple(p.shape)} "
+                f"strides {p.stride()}; the four tensors of a row must be "
+                f"dense with identical strides")
+
+
 def _build_table(batch, device):
     rows = []
-    for p, g, m, master in batch:
+    for i, (p, g, m, master) in enumerate(batch):
+        _check_row(i, p, g, m, master)
         numel = p.numel()
         off = 0
         pp, gp, mp = p.data_ptr(), g.data_ptr(), m.data_ptr()
