@@ -51,6 +51,22 @@ class Conv(nn.Module):
                                residual_post=residual_post,
                                residual_post2=residual_post2)
 
+    def forward_upsampled(self, low, residual_post=None, residual_post2=None):
+        """``forward(ops.upsample2x_nearest(low), ...)`` with the same checks;
+        the op may fold the upsample into the conv on the inference path."""
+        assert low.size(1) == self.inp_dim, \
+            f"input channel {low.size(1)} does not fit kernel channel {self.inp_dim}"
+        if self.dropout and self.training:
+            # dropout masks the upsampled map: keep the two calls
+            return self.forward(ops.upsample2x_nearest(low),
+                                residual_post=residual_post,
+                                residual_post2=residual_post2)
+        return ops.upsample_conv_bn_act(low, self.conv, self.bn,
+                                        act=self.relu is not None,
+                                        residual_post=residual_post,
+                                        residual_post2=residual_post2,
+                                        training=self.training)
+
     def group_item(self, x, residual_post=None, residual_post2=None):
         """This module's ``forward(x, ...)`` as a member of
         ``ops.conv_bn_act_group``: same checks, dropout and training flag."""
@@ -240,13 +256,19 @@ class Hourglass(nn.Module):
             low2 = self._forward(d + 1, low1, up_fms)
         low3 = self.hg[d][2](low2)
         up_fms.append(low2)
-        up2 = ops.upsample2x_nearest(low3)
         # the up1 + deconv1 skip join rides the refine conv's epilogue
         # (post-act residual) instead of a separate elementwise kernel;
         # at d=0 the caller's cross-stack feature-cache add joins too
         # (legal only for the top scale — deeper low2 outputs feed the
-        # internal up-path, which must see them WITHOUT the cache add)
-        return self.hg[d][3](up2, residual_post=up1, residual_post2=post_add)
+        # internal up-path, which must see them WITHOUT the cache add).
+        # The nearest x2 upsample in front of the refine conv is folded into
+        # the conv where the op allows it (bf16 inference).
+        refine = self.hg[d][3]
+        if hasattr(refine, "forward_upsampled"):
+            return refine.forward_upsampled(low3, residual_post=up1,
+                                            residual_post2=post_add)
+        return refine(ops.upsample2x_nearest(low3), residual_post=up1,
+                      residual_post2=post_add)
 
     def forward(self, x, post_add=None):
         up_fms = []

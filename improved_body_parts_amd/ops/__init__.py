@@ -61,6 +61,23 @@ def conv_bn_act(x, conv, bn, act: bool, training: bool,
     return y
 
 
+def upsample_conv_bn_act(low, conv, bn, act: bool, residual_post=None,
+                         residual_post2=None, training: bool = False):
+    """``conv_bn_act(upsample2x_nearest(low), ...)`` — the hourglass refine
+    layer. On the HIP bf16 inference path an eligible 3x3 conv runs as four
+    2x2 convs over ``low`` itself, one per output parity, and the upsampled
+    map is never written (see ``conv.upsample_conv_bn_act_hip``; switch off
+    with ``IBP_UPCONV_FOLD=0``). Elsewhere it is the two calls."""
+    if use_hip_for(low):
+        from . import conv as _conv
+        return _conv.upsample_conv_bn_act_hip(
+            low, conv, bn, act=act, training=training,
+            residual_post=residual_post, residual_post2=residual_post2)
+    return conv_bn_act(upsample2x_nearest(low), conv, bn, act=act,
+                       training=training, residual_post=residual_post,
+                       residual_post2=residual_post2)
+
+
 def conv_bn_add_act(x, conv, bn, residual, act: bool, training: bool,
                     residual_post=None):
     """conv -> (bn) -> += residual -> (leaky_relu); the fused tail of a Residual block."""

@@ -286,6 +286,39 @@ def conv_bn_act_hip(x, conv, bn, act: bool, residual=None, training: bool = Fals
         bn_training, bn, inference)
 
 
+def upconv_fold_enabled() -> bool:
+    """``IBP_UPCONV_FOLD=0`` (read at call time) restores the separate
+    upsample kernel and the 3x3 conv over the upsampled map for A/B runs."""
+    import os
+    return os.environ.get("IBP_UPCONV_FOLD", "1") != "0"
+
+
+def upsample_conv_bn_act_hip(low, conv, bn, act: bool, training: bool = False,
+                             residual_post=None, residual_post2=None):
+    """``conv_bn_act_hip(upsample2x_nearest(low), ...)``. On the bf16
+    inference path (grad disabled, BN in eval mode) a 3x3 stride-1 pad-1 conv
+    with Cin % 64 == 0 and Cout % 8 == 0 runs as four parity 2x2 convs over
+    ``low`` itself (``conv_kernels.upfold_fwd``); everything else runs the
+    upsample kernel and the conv as two calls."""
+    bn_training = training and (bn is not None and bn.training)
+    if not bn_training and not torch.is_grad_enabled() \
+            and upconv_fold_enabled():
+        from . import conv_kernels
+        if conv_kernels.upfold_supported(low, conv.weight, conv.stride,
+                                         conv.padding, conv.dilation):
+            scale, shift = _inference_epilogue(
+                conv.weight, conv.bias,
+                bn.weight if bn is not None else None,
+                bn.bias if bn is not None else None, bn)
+            return conv_kernels.upfold_fwd(
+                _to_cl(low), conv.weight, scale=scale, shift=shift, act=act,
+                residual_post=residual_post, residual_post2=residual_post2)
+    from . import spatial
+    return conv_bn_act_hip(spatial.upsample2x_hip(low), conv, bn, act=act,
+                           training=training, residual_post=residual_post,
+                           residual_post2=residual_post2)
+
+
 def conv_group_enabled() -> bool:
     """``IBP_CONV_GROUP=0`` (read at call time) restores one launch per conv
     for A/B runs."""

@@ -275,6 +275,91 @@ def conv_fwd_group(members):
     return [y.permute(0, 3, 1, 2) for y in ys]
 
 
+# ---------------------------------------------------------------------------
+# nearest-x2 upsample folded into the 3x3 conv that follows it
+# ---------------------------------------------------------------------------
+# A 3x3 conv over a nearest-x2 image multiplies each low-resolution pixel by
+# two or three weights and adds the products. Per output parity (py, px) the
+# layer is a 2x2 conv over the low-resolution map:
+#   y[n, 2i+py, 2j+px] = sum_{a,b} E[py][px][a][b] . x_low[n, i+a-(1-py), j+b-(1-px)]
+#   E[py][px][a][b]    = sum_{kh in R(py,a)} sum_{kw in R(px,b)} W[kh][kw]
+#   R(0,0)={0}  R(0,1)={1,2}  R(1,0)={0,1}  R(1,1)={2}
+# with zeros outside the low-resolution map (the full-resolution zero padding
+# lands on low-resolution index -1 / H). 4/9 of the MACs, no upsampled tensor.
+
+_UPFOLD_ROWS = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}
+
+
+def upfold_weight_reference(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [4, Cout, 2, 2, Cin] folded weights in the
+    weight's dtype, parity ``py*2+px`` outermost. Pure torch, any device;
+    each sum runs from zero in the accumulation dtype (fp32 for bf16/fp16
+    weights, else the weight's own) with kh ascending, then kw — the order of
+    ``pack_upfold_weight_kernel`` — and is rounded once."""
+    cout, cin, kh, kw = weight.shape
+    assert kh == 3 and kw == 3
+    acc_t = torch.float32 if weight.dtype in (torch.bfloat16, torch.float16) \
+        else weight.dtype
+    w = weight.detach().to(acc_t)
+    out = torch.zeros(4, cout, 2, 2, cin, dtype=acc_t, device=weight.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    acc = out[py * 2 + px, :, a, b]
+                    for r in _UPFOLD_ROWS[(py, a)]:
+                        for c in _UPFOLD_ROWS[(px, b)]:
+                            acc += w[:, :, r, c]
+    return out.to(weight.dtype)
+
+
+def upfold_packed_weight(weight: torch.Tensor) -> torch.Tensor:
+    """bf16 [4][Cout][4*Cin] folded packs of a 3x3 weight, one
+    ``pack_upfold_weight_kernel`` launch per weight version."""
+    def pack(w):
+        cout, cin = w.shape[:2]
+        if w.is_cuda:
+            out = torch.empty(4, cout, 4 * cin, dtype=torch.bfloat16,
+                              device=w.device)
+            hip_extension().pack_upfold_weight(w.contiguous(), out)
+            return out
+        return upfold_weight_reference(w).reshape(4, cout, 4 * cin)
+    return _cached_pack(weight, "upfold", pack)
+
+
+def upfold_supported(x, weight, stride, padding, dilation) -> bool:
+    """Envelope of :func:`upfold_fwd`: bf16 CUDA input, 3x3 stride-1 pad-1
+    undilated conv, Cin % 64 == 0 (every K-chunk inside one tap) and
+    Cout % 8 == 0 (16-byte stores)."""
+    cout, cin, kh, kw = weight.shape
+    return (not DISABLE and x.is_cuda and x.dtype == torch.bfloat16
+            and (kh, kw) == (3, 3) and tuple(stride) == (1, 1)
+            and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1)
+            and x.shape[1] == cin and cin % 64 == 0 and cout % 8 == 0)
+
+
+def upfold_fwd(x_low, weight, scale=None, shift=None, act=False,
+               residual_post=None, residual_post2=None):
+    """``conv_fwd(upsample2x_nearest(x_low), weight, pad 1, ...)`` without the
+    upsampled tensor: four parity 2x2 convs in one grouped launch, each
+    storing its own pixels of the full-resolution output. The folded weights
+    carry one more bf16 rounding than the 3x3 pack (docs/KERNELS.md)."""
+    ext = hip_extension()
+    x = x_low.contiguous(memory_format=_CL)
+    n, cin, h, w_ = x.shape
+    cout = weight.shape[0]
+    post = [None, None]
+    for i, r in enumerate((residual_post, residual_post2)):
+        if r is not None:
+            assert tuple(r.shape) == (n, cout, 2 * h, 2 * w_), \
+                f"residual {tuple(r.shape)} is not the upsampled output shape"
+            post[i] = r.contiguous(memory_format=_CL).permute(0, 2, 3, 1)
+    y = ext.conv_mfma_upfold_fwd(x.permute(0, 2, 3, 1),
+                                 upfold_packed_weight(weight), n, h, w_, cin,
+                                 cout, scale, shift, act, post[0], post[1])
+    return y.permute(0, 3, 1, 2)
+
+
 def conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
     """dx = stride-1 conv of the (virtually) zero-dilated dy with 180-rotated
     transposed weights; pad' = dil*(K-1) - pad, gather stride zs = stride."""

@@ -83,6 +83,16 @@ std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K);
 void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
                       const c10::optional<Tensor>& dgrad_pack);
 
+void pack_upfold_weight(const Tensor& w, Tensor& out);
+Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
+                            int64_t N, int64_t H, int64_t W, int64_t Cin,
+                            int64_t Cout, const c10::optional<Tensor>& scale,
+                            const c10::optional<Tensor>& shift, bool act,
+                            const c10::optional<Tensor>& residual_post,
+                            const c10::optional<Tensor>& residual_post2);
+std::vector<int64_t> conv_mfma_upfold_plan(int64_t M_low, int64_t Cout,
+                                           int64_t Cin);
+
 // conv_wgrad.hip
 Tensor conv_mfma_wgrad(const Tensor& x, const Tensor& dy, int64_t N, int64_t H,
                        int64_t W, int64_t Cin, int64_t Cout, int64_t KH,
@@ -170,6 +180,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pack_conv_weight", &pack_conv_weight,
         "fwd + dgrad weight packs in one kernel",
         py::arg("w"), py::arg("fwd_pack"), py::arg("dgrad_pack") = c10::nullopt);
+  m.def("pack_upfold_weight", &pack_upfold_weight,
+        "3x3 weight -> four folded 2x2 packs [4][Cout][4*Cin] (nearest-x2 "
+        "upsample folded into the conv)",
+        py::arg("w"), py::arg("out"));
+  m.def("conv_mfma_upfold_fwd", &conv_mfma_upfold_fwd,
+        "conv3x3(nearest_x2(x_low)) + epilogue as four parity 2x2 convs in "
+        "one grouped launch",
+        py::arg("x_low"), py::arg("packs"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("scale") = c10::nullopt, py::arg("shift") = c10::nullopt,
+        py::arg("act") = false, py::arg("residual_post") = c10::nullopt,
+        py::arg("residual_post2") = c10::nullopt);
+  m.def("conv_mfma_upfold_plan", &conv_mfma_upfold_plan,
+        "debug: [BM, BN, splitk, deep] shared by the four parities of an "
+        "upfold conv over M_low low-resolution pixels",
+        py::arg("M_low"), py::arg("Cout"), py::arg("Cin"));
   m.def("conv_mfma_wgrad", &conv_mfma_wgrad,
         "MFMA implicit-GEMM conv weight gradient (tr16 LDS transpose)");
   m.def("conv_wgrad_plan", &conv_wgrad_plan,

@@ -24,6 +24,11 @@
 //   * zs (gather stride): reads the virtual zero-dilated image x[hi/zs] when
 //     hi % zs == 0 — stride-s dgrad as a stride-1 conv over dilated dy with
 //     180-rotated transposed weights.
+//   * up (output scatter): a 3x3 conv over a nearest-x2 upsampled map runs as
+//     four 2x2 convs over the low-resolution map, one per output parity, with
+//     summed weights (pack_upfold_weight_kernel); each parity's rows are
+//     stored at its own pixels of the full-resolution output
+//     (conv_mfma_upfold_fwd).
 //
 // Supported: any KHxKW with Cin % 8 == 0 (per-8 subpieces re-derive their
 // filter tap, so Cin 16 s2d-stem tiles and 64..768 hourglass tiles both hit
@@ -69,6 +74,10 @@ struct ConvParams {
   int vec_epi;               // 1: 4-channel epilogue groups, 2: 8-channel
   int pair_epi;              // fallback may use 2-channel (4-byte) accesses
   int m32;                   // M (+ tile padding) fits 32-bit index math
+  // output scatter (nearest-x2 upsample folded into the conv): rows index the
+  // LOW-resolution Ho x Wo grid and row (n, i, j) is stored at pixel
+  // (n*2Ho + 2i+py)*2Wo + 2j+px of y / res / res_post / res_post2
+  int up, py, px;
 };
 
 // LDS tile addressing: unpadded BK-short rows with a T2 XOR swizzle — the
@@ -87,7 +96,11 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 // grouped kernel (several independent convs in one launch) share it: `bid`
 // is the block id LOCAL to this problem, lds_a/lds_b hold 2*BM*BK and
 // 2*BN*BK shorts (double buffer).
-template <int BM, int BN, bool DEEP, typename Params>
+//
+// UP compiles the output scatter of ConvParams::up in; only the grouped
+// upfold kernel instantiates it, every other kernel is the code it was
+// without it.
+template <int BM, int BN, bool DEEP, bool UP, typename Params>
 __device__ __forceinline__ void conv_mfma_body(const Params& p,
                                                const int bid,
                                                unsigned short* lds_a,
@@ -381,6 +394,33 @@ a_done:
   const int ech4 = (lane >> 4) * 4;
   float* const ws_slice =
       p.splitk > 1 ? p.ws + (long long)sk * p.M * p.Cout : nullptr;
+  // UP: output pixel of each of this lane's AFRAG rows (16 apart) — the
+  // first row is decomposed once in 32-bit math (the host only sets `up`
+  // with m32), the rest carry-walk; the fp32 slabs stay in row order, their
+  // combine does the same scatter.
+  long long opix[UP ? AFRAG : 1];
+  if constexpr (UP) {
+    unsigned t = (unsigned)(m0 + row_base + epix);
+    int oj = (int)(t % (unsigned)p.Wo); t /= (unsigned)p.Wo;
+    int oi = (int)(t % (unsigned)p.Ho);
+    int on = (int)(t / (unsigned)p.Ho);
+    #pragma unroll
+    for (int i = 0; i < AFRAG; ++i) {
+      opix[i] = ((long long)on * (2 * p.Ho) + 2 * oi + p.py) * (2 * p.Wo) +
+                2 * oj + p.px;
+      oj += 16;
+      while (oj >= p.Wo) {
+        oj -= p.Wo;
+        if (++oi == p.Ho) { oi = 0; ++on; }
+      }
+    }
+  }
+  // element index in y / residuals of (row slot i, channel c), given the
+  // row-order index `lin` = m * Cout + c that the slabs use
+  auto out_idx = [&](int i, int c, long long lin) -> long long {
+    if constexpr (UP) return opix[i] * p.Cout + c;
+    else return lin;
+  };
   // fused epilogue of one fragment: 8-byte residual loads, today's order
   auto finish = [&](const floatx4& a, long long idx, const floatx4& sc,
                     const floatx4& sh) -> ushortv4 {
@@ -425,7 +465,7 @@ a_done:
       for (int i = 0; i < AFRAG; ++i) {
         const long long m = m0 + row_base + i * 16 + epix;
         if (m >= p.M) continue;
-        const long long idx0 = m * p.Cout + col0;
+        const long long idx0 = out_idx(i, col0, m * p.Cout + col0);
         union { ushortv4 v; unsigned u[2]; } o0, o1, rx;
         o0.v = finish(acc[i][jp], idx0, sc0, sh0);
         o1.v = ushortv4{0, 0, 0, 0};
@@ -463,13 +503,14 @@ a_done:
       for (int i = 0; i < AFRAG; ++i) {
         const long long m = m0 + row_base + i * 16 + epix;
         if (m >= p.M) continue;
-        const long long idx = m * p.Cout + col;
+        const long long lin = m * p.Cout + col;
         if (p.splitk > 1) {
           // each K-split owns a workspace slice: plain stores, no zero-init,
           // no atomics, deterministic sums (combine kernel reduces slices)
-          *reinterpret_cast<floatx4*>(ws_slice + idx) = acc[i][j];
+          *reinterpret_cast<floatx4*>(ws_slice + lin) = acc[i][j];
           continue;
         }
+        const long long idx = out_idx(i, col, lin);
         *reinterpret_cast<ushortv4*>(p.y + idx) =
             finish(acc[i][j], idx, sc, sh);
       }
@@ -489,12 +530,13 @@ a_done:
         for (int i = 0; i < AFRAG; ++i) {
           const long long m = m0 + row_base + i * 16 + epix;
           if (m >= p.M) continue;
-          const long long idx = m * p.Cout + col + r;
+          const long long lin = m * p.Cout + col + r;
           if (p.splitk > 1) {
-            *reinterpret_cast<floatx2*>(ws_slice + idx) =
+            *reinterpret_cast<floatx2*>(ws_slice + lin) =
                 floatx2{acc[i][j][r], acc[i][j][r + 1]};
             continue;
           }
+          const long long idx = out_idx(i, col + r, lin);
           unsigned r0 = 0, r1 = 0, r2 = 0;
           if (p.res) r0 = *reinterpret_cast<const unsigned*>(p.res + idx);
           if (p.res_post)
@@ -529,11 +571,12 @@ a_done:
       for (int i = 0; i < AFRAG; ++i) {
         const long long m = m0 + row_base + i * 16 + epix;
         if (m >= p.M) continue;
-        const long long idx = m * p.Cout + col + r;
+        const long long lin = m * p.Cout + col + r;
         if (p.splitk > 1) {
-          ws_slice[idx] = acc[i][j][r];
+          ws_slice[lin] = acc[i][j][r];
           continue;
         }
+        const long long idx = out_idx(i, col + r, lin);
         float v = acc[i][j][r] * sc + sh;
         if (p.res) v += us2f(p.res[idx]);
         if (p.act) v = leaky(v, 0.01f);
@@ -549,7 +592,7 @@ template <int BM, int BN, bool DEEP = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
   __shared__ unsigned short lds_a[2 * BM * BK];
   __shared__ unsigned short lds_b[2 * BN * BK];
-  conv_mfma_body<BM, BN, DEEP>(p, blockIdx.x, lds_a, lds_b);
+  conv_mfma_body<BM, BN, DEEP, false>(p, blockIdx.x, lds_a, lds_b);
 }
 
 // ---- grouped launch --------------------------------------------------------
@@ -575,6 +618,9 @@ constexpr int tile_cfg(int BM, int BN, bool deep) {
          (deep ? 1 : 0);
 }
 
+// <true> is the upfold launch: every problem is one output parity of a
+// nearest-x2-upsample-folded conv and scatters its rows (ConvParams::up).
+template <bool UP>
 __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
     ConvGroupParams g) {
   // one static buffer sized for the largest tile (128x128: 2 x 32 KB); the
@@ -603,21 +649,21 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
   const int bid = gb - base;
   switch (cfg) {
     case tile_cfg(128, 128, false):
-      conv_mfma_body<128, 128, false>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 128, false, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 128, true):
-      conv_mfma_body<128, 128, true>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 128, true, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 64, false):
-      conv_mfma_body<128, 64, false>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 64, false, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 64, true):
-      conv_mfma_body<128, 64, true>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 64, true, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(64, 64, false):
-      conv_mfma_body<64, 64, false>(p, bid, lds, lds + 2 * 64 * BK); break;
+      conv_mfma_body<64, 64, false, UP>(p, bid, lds, lds + 2 * 64 * BK); break;
     case tile_cfg(64, 64, true):
-      conv_mfma_body<64, 64, true>(p, bid, lds, lds + 2 * 64 * BK); break;
+      conv_mfma_body<64, 64, true, UP>(p, bid, lds, lds + 2 * 64 * BK); break;
     case tile_cfg(32, 64, false):
-      conv_mfma_body<32, 64, false>(p, bid, lds, lds + 2 * 32 * BK); break;
+      conv_mfma_body<32, 64, false, UP>(p, bid, lds, lds + 2 * 32 * BK); break;
     default:
-      conv_mfma_body<32, 64, true>(p, bid, lds, lds + 2 * 32 * BK); break;
+      conv_mfma_body<32, 64, true, UP>(p, bid, lds, lds + 2 * 32 * BK); break;
   }
 }
 
@@ -625,8 +671,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
 // segment: it must stay the kernel's ONLY explicit argument (explicit
 // arguments come first in the segment, hidden ones after), with the problem
 // array leading the struct.
-static_assert(std::is_same<decltype(&conv_mfma_grouped_kernel),
-                           void (*)(ConvGroupParams)>::value,
+static_assert(std::is_same<decltype(&conv_mfma_grouped_kernel<false>),
+                           void (*)(ConvGroupParams)>::value &&
+                  std::is_same<decltype(&conv_mfma_grouped_kernel<true>),
+                               void (*)(ConvGroupParams)>::value,
               "conv_mfma_grouped_kernel must take the table as its only "
               "argument: it is read at kernarg offset 0");
 static_assert(offsetof(ConvGroupParams, p) == 0 &&
@@ -658,14 +706,30 @@ __device__ __forceinline__ float combine_one(float v, float sc, float sh,
 // walked incrementally, one 64-bit modulo per thread instead of per element.
 // `bid` / `nblocks` are the block id and block count LOCAL to this problem
 // (the grouped combine runs several problems in one grid).
-template <bool VEC>
+//
+// Output scatter (ConvParams::up): the slabs are in the problem's row order,
+// y and the residuals are addressed at the row's full-resolution pixel. The
+// host sets `up` only when the row count fits 32 bits.
+struct OutScatter {
+  int up, py, px, Ho, Wo;
+};
+
+__device__ __forceinline__ long long scatter_pixel(unsigned m,
+                                                   const OutScatter& s) {
+  const unsigned j = m % (unsigned)s.Wo; m /= (unsigned)s.Wo;
+  const unsigned i = m % (unsigned)s.Ho;
+  const unsigned n = m / (unsigned)s.Ho;
+  return ((long long)n * (2 * s.Ho) + 2 * i + s.py) * (2 * s.Wo) + 2 * j + s.px;
+}
+
+template <bool VEC, bool UP>
 __device__ __forceinline__ void splitk_combine_body(
     const float* __restrict__ ws, unsigned short* __restrict__ y,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const unsigned short* __restrict__ res,
     const unsigned short* __restrict__ res_post,
     const unsigned short* __restrict__ res_post2, long long total, int C,
-    int act, int splitk, int bid, int nblocks) {
+    int act, int splitk, int bid, int nblocks, const OutScatter& os) {
   if constexpr (VEC) {
     const int C8 = C >> 3;
     const long long groups = total >> 3;
@@ -674,11 +738,15 @@ __device__ __forceinline__ void splitk_combine_body(
     if (g >= groups) return;
     int c8 = (int)(g % C8);
     const int cstep = (int)(step % C8);
+    // scattered output: the row index is walked beside the channel group
+    unsigned row = UP ? (unsigned)(g / C8) : 0u;
+    const unsigned rstep = UP ? (unsigned)(step / C8) : 0u;
     for (; g < groups; g += step) {
-      const long long i = g << 3;
+      const long long w = g << 3;
+      const long long i = UP ? scatter_pixel(row, os) * C + c8 * 8 : w;
       floatx4 lo = floatx4{0.f, 0.f, 0.f, 0.f}, hi = lo;
       for (int s = 0; s < splitk; ++s) {
-        const float* src = ws + (long long)s * total + i;
+        const float* src = ws + (long long)s * total + w;
         lo += *reinterpret_cast<const floatx4*>(src);
         hi += *reinterpret_cast<const floatx4*>(src + 4);
       }
@@ -708,13 +776,19 @@ __device__ __forceinline__ void splitk_combine_body(
       *reinterpret_cast<ushortv8*>(y + i) = out;
       c8 += cstep;
       if (c8 >= C8) c8 -= C8;
+      if constexpr (UP) {
+        row += rstep;
+        if (c8 < cstep) ++row;   // the channel group wrapped
+      }
     }
   } else {
-    for (long long i = bid * (long long)blockDim.x + threadIdx.x;
-         i < total; i += (long long)nblocks * blockDim.x) {
-      int c = (int)(i % C);
+    for (long long w = bid * (long long)blockDim.x + threadIdx.x;
+         w < total; w += (long long)nblocks * blockDim.x) {
+      int c = (int)(w % C);
+      const long long i =
+          UP ? scatter_pixel((unsigned)(w / C), os) * C + c : w;
       float v = 0.f;
-      for (int s = 0; s < splitk; ++s) v += ws[(long long)s * total + i];
+      for (int s = 0; s < splitk; ++s) v += ws[(long long)s * total + w];
       v = combine_one(v, scale ? scale[c] : 1.f, scale ? shift[c] : 0.f,
                       scale != nullptr, res != nullptr,
                       res ? us2f(res[i]) : 0.f, act, res_post != nullptr,
@@ -736,9 +810,10 @@ __global__ void splitk_combine_kernel(const float* __restrict__ ws,
                                       const unsigned short* __restrict__ res_post2,
                                       long long total, int C, int act,
                                       int splitk) {
-  splitk_combine_body<VEC>(ws, y, scale, shift, res, res_post, res_post2,
-                           total, C, act, splitk, (int)blockIdx.x,
-                           (int)gridDim.x);
+  splitk_combine_body<VEC, false>(ws, y, scale, shift, res, res_post,
+                                  res_post2, total, C, act, splitk,
+                                  (int)blockIdx.x, (int)gridDim.x,
+                                  OutScatter{});
 }
 
 // grouped combine: the split members of one grouped conv launch, same
@@ -754,6 +829,7 @@ struct CombineProblem {
   const unsigned short* res_post2;
   long long total;
   int C, act, splitk, vec;
+  OutScatter os;
 };
 
 struct CombineGroupParams {
@@ -762,6 +838,7 @@ struct CombineGroupParams {
   int n;
 };
 
+template <bool UP>
 __global__ void splitk_combine_grouped_kernel(CombineGroupParams g) {
   const int gb = blockIdx.x;
   int pi = 0, base = 0;
@@ -775,13 +852,44 @@ __global__ void splitk_combine_grouped_kernel(CombineGroupParams g) {
   const CombineProblem& c = g.c[pi];
   const int nblocks = g.block_end[pi] - base;
   if (c.vec)
-    splitk_combine_body<true>(c.ws, c.y, c.scale, c.shift, c.res, c.res_post,
-                              c.res_post2, c.total, c.C, c.act, c.splitk,
-                              gb - base, nblocks);
+    splitk_combine_body<true, UP>(c.ws, c.y, c.scale, c.shift, c.res,
+                                  c.res_post, c.res_post2, c.total, c.C,
+                                  c.act, c.splitk, gb - base, nblocks, c.os);
   else
-    splitk_combine_body<false>(c.ws, c.y, c.scale, c.shift, c.res, c.res_post,
-                               c.res_post2, c.total, c.C, c.act, c.splitk,
-                               gb - base, nblocks);
+    splitk_combine_body<false, UP>(c.ws, c.y, c.scale, c.shift, c.res,
+                                   c.res_post, c.res_post2, c.total, c.C,
+                                   c.act, c.splitk, gb - base, nblocks, c.os);
+}
+
+// upfold weight pack: [Cout][Cin][3][3] -> [4][Cout][4*Cin], parity
+// py*2+px outermost, then tap-major (a, b) with the channel fastest, like the
+// forward pack. A 3x3 conv over a nearest-x2 image is, per output parity, a
+// 2x2 conv over the low-resolution map whose weights are sums of 1, 2 or 4
+// of the 3x3 weights: rows R(0,0)={0} R(0,1)={1,2} R(1,0)={0,1} R(1,1)={2}
+// (same for columns). Summed in fp32 from 0.f, kh ascending then kw, rounded
+// to bf16 once (round to nearest even).
+__global__ void pack_upfold_weight_kernel(const unsigned short* __restrict__ w,
+                                          unsigned short* __restrict__ out,
+                                          int Cout, int Cin) {
+  const long long per = (long long)Cout * 4 * Cin;
+  const long long total = 4 * per;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int ci = (int)(i % Cin);
+    long long t = i / Cin;
+    const int tap = (int)(t & 3); t >>= 2;
+    const int co = (int)(t % Cout);
+    const int par = (int)(t / Cout);
+    const int py = par >> 1, px = par & 1, a = tap >> 1, b = tap & 1;
+    // R(p, t) = [lo, hi]
+    const int kh_lo = py == 0 ? a : 2 * a, kh_hi = py == 0 ? 2 * a : a + 1;
+    const int kw_lo = px == 0 ? b : 2 * b, kw_hi = px == 0 ? 2 * b : b + 1;
+    const unsigned short* src = w + ((long long)co * Cin + ci) * 9;
+    float acc = 0.f;
+    for (int kh = kh_lo; kh <= kh_hi; ++kh)
+      for (int kw = kw_lo; kw <= kw_hi; ++kw) acc += us2f(src[kh * 3 + kw]);
+    out[i] = f2us(acc);
+  }
 }
 
 // weight pack: [Cout,Cin,KH,KW] (standard contiguous) -> fwd [Cout][f*Cin+ci]
@@ -863,8 +971,8 @@ struct TilePlan {
   bool deep;
 };
 
-TilePlan plan_tile(long long M, int Cout, int K) {
-  TilePlan t;
+// BM x BN for a GEMM with M rows
+void pick_tile(long long M, int Cout, int& BM_out, int& BN_out) {
   // ---- tile selection -------------------------------------------------------
   // BM: small-M tiles for the hourglass's 8^2/16^2 scales (avoids the 8-16x
   // split-K workspace round-trip measured in round 1); BN: minimise padded
@@ -876,9 +984,12 @@ TilePlan plan_tile(long long M, int Cout, int K) {
   const long long padded128 = ((Cout + 127) / 128) * 128LL;
   const long long padded64 = ((Cout + 63) / 64) * 64LL;
   int BN = (BM == 128 && Cout > 64 && padded128 <= padded64) ? 128 : 64;
-  t.n_mtiles = (int)((M + BM - 1) / BM);
-  const int ntiles = t.n_mtiles * (int)((Cout + BN - 1) / BN);
-  const int nk_total = (K + ibp::BK - 1) / ibp::BK;
+  BM_out = BM;
+  BN_out = BN;
+}
+
+// split-K factor for a grid of `ntiles` output tiles over nk_total K-chunks
+int pick_split(int ntiles, int nk_total) {
   // split K on small grids so the 256-CU chip stays filled (~2 blocks/CU).
   // Normalise so EVERY slice has work: with raw splitk=7 over nk_total=8 the
   // last 3 slices get no chunks, return early, and the combine kernel then
@@ -893,6 +1004,17 @@ TilePlan plan_tile(long long M, int Cout, int K) {
     int nk_chunk = ((int)nk_total + splitk - 1) / splitk;
     splitk = ((int)nk_total + nk_chunk - 1) / nk_chunk;
   }
+  return splitk;
+}
+
+TilePlan plan_tile(long long M, int Cout, int K) {
+  TilePlan t;
+  int BM, BN;
+  pick_tile(M, Cout, BM, BN);
+  t.n_mtiles = (int)((M + BM - 1) / BM);
+  const int ntiles = t.n_mtiles * (int)((Cout + BN - 1) / BN);
+  const int nk_total = (K + ibp::BK - 1) / ibp::BK;
+  const int splitk = pick_split(ntiles, nk_total);
   t.BM = BM;
   t.BN = BN;
   t.ntiles = ntiles;
@@ -904,6 +1026,16 @@ TilePlan plan_tile(long long M, int Cout, int K) {
   return t;
 }
 
+// One output parity of an upsample-folded conv (see conv_mfma_upfold_fwd):
+// the caller provides the shared full-resolution output, the weight slice of
+// this parity and the tile/split chosen for the four parities together.
+struct UpFold {
+  Tensor y;                  // [N, 2H, 2W, Cout]
+  const unsigned short* w;   // this parity's [Cout][4*Cin] pack
+  int py, px;
+  TilePlan t;
+};
+
 ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
                    int64_t H, int64_t W, int64_t Cin, int64_t Cout,
                    int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
@@ -912,7 +1044,8 @@ ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
                    const c10::optional<Tensor>& shift,
                    const c10::optional<Tensor>& residual, bool act,
                    const c10::optional<Tensor>& residual_post,
-                   const c10::optional<Tensor>& residual_post2, int64_t zs) {
+                   const c10::optional<Tensor>& residual_post2, int64_t zs,
+                   const UpFold* up = nullptr) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::ScalarType::BFloat16);
   TORCH_CHECK(w_packed.is_contiguous());
   ConvPlan plan;
@@ -942,10 +1075,14 @@ ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
   p.act = act ? 1 : 0;
   // any Cin is legal: subpieces crossing tap boundaries take the per-element
   // re-derive path (the Cin=3 stem runs there; Cin % 8 == 0 stays vectorized)
-  plan.y = torch::empty({N, Ho, Wo, Cout}, x.options());
+  plan.y = up ? up->y : torch::empty({N, Ho, Wo, Cout}, x.options());
   p.y = reinterpret_cast<unsigned short*>(plan.y.data_ptr());
+  p.up = up ? 1 : 0;
+  p.py = up ? up->py : 0;
+  p.px = up ? up->px : 0;
+  if (up) p.w = up->w;
 
-  const TilePlan t = plan_tile(p.M, p.Cout, p.K);
+  const TilePlan t = up ? up->t : plan_tile(p.M, p.Cout, p.K);
   const int BM = t.BM, BN = t.BN, splitk = t.splitk;
   p.n_mtiles = t.n_mtiles;
   p.splitk = splitk;
@@ -972,6 +1109,9 @@ ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
         misaligned(p.res, 16) || misaligned(p.res_post, 16) ||
         misaligned(p.res_post2, 16) || misaligned(p.y, 16));
   p.m32 = p.M + BM < (1LL << 31);
+  // the scatter decomposes rows and output pixels' rows in 32-bit math
+  TORCH_CHECK(!up || 4 * p.M + 4 * BM < (1LL << 31),
+              "upfold conv: output too large for 32-bit row math");
   plan.BM = BM;
   plan.BN = BN;
   plan.nblocks = t.ntiles * splitk;
@@ -986,6 +1126,10 @@ void set_workspace(ConvPlan& plan, float* ws) {
   plan.vec_combine = plan.vec_combine && !misaligned(ws, 16);
 }
 
+ibp::OutScatter out_scatter(const ibp::ConvParams& p) {
+  return ibp::OutScatter{p.up, p.py, p.px, p.Ho, p.Wo};
+}
+
 int combine_blocks(const ConvPlan& plan) {
   const long long total = plan.p.M * plan.p.Cout;
   return ibp::grid_1d(plan.vec_combine ? total / 8 : total, 256, 4096);
@@ -993,6 +1137,7 @@ int combine_blocks(const ConvPlan& plan) {
 
 void launch_single(const ConvPlan& plan, hipStream_t stream) {
   const ibp::ConvParams& p = plan.p;
+  TORCH_CHECK(!p.up, "upfold plans launch through launch_group");
   dim3 grid(plan.nblocks), block(256);
   const int BM = plan.BM, BN = plan.BN;
   const bool deep = plan.deep;
@@ -1078,7 +1223,8 @@ void launch_group(std::vector<ConvPlan>& plans, size_t first, size_t last,
     cg.c[nc] = ibp::CombineProblem{p.ws, p.y, p.scale, p.shift, p.res,
                                    p.res_post, p.res_post2,
                                    (long long)p.M * p.Cout, p.Cout, p.act,
-                                   p.splitk, plan.vec_combine ? 1 : 0};
+                                   p.splitk, plan.vec_combine ? 1 : 0,
+                                   out_scatter(p)};
     cg.block_end[nc] = cblocks;
     ++nc;
   }
@@ -1087,11 +1233,23 @@ void launch_group(std::vector<ConvPlan>& plans, size_t first, size_t last,
     cg.block_end[i] = cblocks;
   }
   cg.n = nc;
-  hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel, dim3(blocks), dim3(256), 0,
-                     stream, g);
-  if (nc > 0)
-    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel, dim3(cblocks),
+  // all members scatter (the four parities of an upfold conv) or none does
+  const bool up = plans[first].p.up != 0;
+  for (int i = 0; i < n; ++i)
+    TORCH_CHECK((plans[first + i].p.up != 0) == up,
+                "grouped conv: upfold and plain members cannot mix");
+  if (up)
+    hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel<true>, dim3(blocks),
+                       dim3(256), 0, stream, g);
+  else
+    hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel<false>, dim3(blocks),
+                       dim3(256), 0, stream, g);
+  if (nc > 0 && up)
+    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel<true>, dim3(cblocks),
                        dim3(256), 0, stream, cg);
+  else if (nc > 0)
+    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel<false>,
+                       dim3(cblocks), dim3(256), 0, stream, cg);
 }
 
 }  // namespace
@@ -1176,5 +1334,98 @@ std::vector<Tensor> conv_mfma_fwd_grouped(
 // shape lands on.
 std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K) {
   const TilePlan t = plan_tile(M, (int)Cout, (int)K);
+  return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
+}
+
+// ---- nearest-x2 upsample folded into a 3x3 conv ----------------------------
+void pack_upfold_weight(const Tensor& w, Tensor& out) {
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 4 &&
+              w.scalar_type() == at::ScalarType::BFloat16 &&
+              w.size(2) == 3 && w.size(3) == 3,
+              "pack_upfold_weight: contiguous bf16 [Cout][Cin][3][3]");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+              out.scalar_type() == at::ScalarType::BFloat16 &&
+              out.numel() == 16 * w.size(0) * w.size(1),
+              "pack_upfold_weight: out must be bf16 [4][Cout][4*Cin]");
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  dim3 grid(ibp::grid_1d(out.numel(), 256, 2048)), block(256);
+  hipLaunchKernelGGL(ibp::pack_upfold_weight_kernel, grid, block, 0, stream,
+                     reinterpret_cast<const unsigned short*>(w.data_ptr()),
+                     reinterpret_cast<unsigned short*>(out.data_ptr()),
+                     (int)w.size(0), (int)w.size(1));
+}
+
+namespace {
+
+// The four parities are one logical conv: tile from M = 4*M_low rows, split
+// from all 4*ntiles tiles, the same choice for every parity. (Planned one by
+// one, the 128^2 refine conv would take BM=64 and split 2 although its 1024
+// tiles already fill the chip.) Tiles do not straddle parities, so n_mtiles
+// and ntiles are per parity.
+TilePlan plan_upfold_tile(long long M_low, int Cout, int Cin) {
+  TilePlan t;
+  pick_tile(4 * M_low, Cout, t.BM, t.BN);
+  t.n_mtiles = (int)((M_low + t.BM - 1) / t.BM);
+  t.ntiles = t.n_mtiles * ((Cout + t.BN - 1) / t.BN);
+  const int nk_total = (4 * Cin + ibp::BK - 1) / ibp::BK;
+  t.splitk = pick_split(4 * t.ntiles, nk_total);
+  t.nk_block = (nk_total + t.splitk - 1) / t.splitk;
+  t.deep = t.nk_block <= 6;
+  return t;
+}
+
+}  // namespace
+
+// y[N, 2H, 2W, Cout] = epilogue(conv3x3(nearest_x2(x_low), W, pad 1)) as
+// four stride-1 2x2 convs over x_low [N, H, W, Cin], one per output parity
+// (py, px), with pad (1-py, 1-px) and the folded weights of
+// pack_upfold_weight; each stores into its own pixels of the shared output.
+// One grouped conv launch, at most one grouped combine.
+Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
+                            int64_t N, int64_t H, int64_t W, int64_t Cin,
+                            int64_t Cout, const c10::optional<Tensor>& scale,
+                            const c10::optional<Tensor>& shift, bool act,
+                            const c10::optional<Tensor>& residual_post,
+                            const c10::optional<Tensor>& residual_post2) {
+  TORCH_CHECK(x_low.is_cuda() && x_low.is_contiguous() &&
+              x_low.numel() == N * H * W * Cin,
+              "conv_mfma_upfold_fwd: x_low must be contiguous [N][H][W][Cin]");
+  TORCH_CHECK(packs.is_cuda() && packs.is_contiguous() &&
+              packs.scalar_type() == at::ScalarType::BFloat16 &&
+              packs.numel() == 16 * Cout * Cin,
+              "conv_mfma_upfold_fwd: packs must be bf16 [4][Cout][4*Cin]");
+  for (const auto* r : {&residual_post, &residual_post2})
+    TORCH_CHECK(!r->has_value() ||
+                ((*r)->is_cuda() &&
+                 (*r)->scalar_type() == at::ScalarType::BFloat16 &&
+                 (*r)->numel() == 4 * N * H * W * Cout),
+                "conv_mfma_upfold_fwd: residuals must be bf16 "
+                "[N][2H][2W][Cout]");
+  UpFold up;
+  up.y = torch::empty({N, 2 * H, 2 * W, Cout}, x_low.options());
+  up.t = plan_upfold_tile((long long)N * H * W, (int)Cout, (int)Cin);
+  std::vector<ConvPlan> plans;
+  plans.reserve(4);
+  for (int par = 0; par < 4; ++par) {
+    up.py = par >> 1;
+    up.px = par & 1;
+    up.w = reinterpret_cast<const unsigned short*>(packs.data_ptr()) +
+           (long long)par * Cout * 4 * Cin;
+    plans.push_back(plan_conv(x_low, packs, N, H, W, Cin, Cout, 2, 2, 1,
+                              1 - up.py, 1 - up.px, 1, 1, H, W, scale, shift,
+                              c10::nullopt, act, residual_post,
+                              residual_post2, 1, &up));
+  }
+  std::vector<Tensor> keep;
+  launch_group(plans, 0, 4, x_low.options().dtype(torch::kFloat32),
+               at::hip::getCurrentHIPStream().stream(), keep);
+  return up.y;
+}
+
+// {BM, BN, splitk, deep} shared by the four parities of an upfold conv over
+// M_low = N*H*W low-resolution pixels.
+std::vector<int64_t> conv_mfma_upfold_plan(int64_t M_low, int64_t Cout,
+                                           int64_t Cin) {
+  const TilePlan t = plan_upfold_tile(M_low, (int)Cout, (int)Cin);
   return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
 }
