@@ -10,10 +10,14 @@ Replaces: nn.Conv2d -> nn.BatchNorm2d -> nn.LeakyReLU chains
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn.functional as F
 
+from . import conv_kernels
 from ._backend import hip_extension
+from ._cache import versioned
 
 LEAKY_SLOPE = 0.01
 _CL = torch.channels_last
@@ -26,7 +30,6 @@ def _to_cl(t):
 def _conv_forward(x, weight, bias, stride, padding, dilation):
     """Convolution forward dispatch: MFMA implicit-GEMM kernel when the shape is
     supported, library fallback otherwise (first iterations / odd shapes)."""
-    from . import conv_kernels
     y = conv_kernels.conv_fwd(x, weight, stride, padding, dilation)
     if y is None:
         y = F.conv2d(x, weight, None, stride, padding, dilation)
@@ -37,7 +40,6 @@ def _conv_forward(x, weight, bias, stride, padding, dilation):
 
 
 def _conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
-    from . import conv_kernels
     dx = conv_kernels.conv_dgrad(dy, weight, x_shape, stride, padding, dilation)
     if dx is None:
         dx = torch.nn.grad.conv2d_input(x_shape, weight, dy, stride, padding,
@@ -47,7 +49,6 @@ def _conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
 
 
 def _conv_wgrad(x, dy, w_shape, stride, padding, dilation):
-    from . import conv_kernels
     dw = conv_kernels.conv_wgrad(x, dy, w_shape, stride, padding, dilation)
     if dw is None:
         dw = torch.nn.grad.conv2d_weight(x, w_shape, dy, stride, padding,
@@ -55,45 +56,45 @@ def _conv_wgrad(x, dy, w_shape, stride, padding, dilation):
     return dw
 
 
-_BIAS_FOLD = {}
+def _on_inference_path(x, bn, training):
+    """The bf16 inference path (the conv kernel's epilogue does the whole
+    module): bf16 input, BN (if any) in eval mode, grad disabled — read here,
+    outside ``Function.apply``; inside ``forward`` it is always off."""
+    return not _bn_training(bn, training) and not torch.is_grad_enabled() \
+        and x.dtype == torch.bfloat16
 
 
-def _bias_fold(weight, bias):
-    """(ones, bias.float()) for the bias-only epilogue, cached against the
-    bias version — a fresh pair per call was ~60 FillFunctor/copy launches
-    per inference step (the 1x1 heads carry biases)."""
-    import weakref
-    key = id(bias)
-    entry = _BIAS_FOLD.get(key)
-    ver = bias._version
-    if entry is not None and entry[0] == ver:
-        return entry[1], entry[2]
-    scale = torch.ones(weight.shape[0], device=bias.device, dtype=torch.float32)
-    shift = bias.detach().float()
-    if entry is None:
-        weakref.finalize(bias, _BIAS_FOLD.pop, key, None)
-    _BIAS_FOLD[key] = (ver, scale, shift)
-    return scale, shift
+def _bn_training(bn, training):
+    return training and bn is not None and bn.training
 
 
-def _inference_epilogue(weight, bias, gamma, beta, bn_mod):
+def _inference_epilogue(conv, bn):
     """(scale, shift) of the conv kernel's fused epilogue on the inference
-    path: the folded eval-mode BN (cached on the BN module against the
-    parameter versions), else the bias-only pair, else (None, None)."""
+    path: the folded eval-mode BN, else the bias-only pair (ones, bias), else
+    (None, None). Cached against parameter versions (``bn.bias`` is not in the
+    key): fresh tensors per call were ~60 fill/copy launches per step."""
+    gamma = bn.weight if bn is not None else None
     if gamma is not None:
-        ver = (gamma._version, bn_mod.running_mean._version,
-               bn_mod.running_var._version)
-        cached = getattr(bn_mod, "_ibp_folded", None)
-        if cached is not None and cached[0] == ver:
-            return cached[1], cached[2]
-        invstd = torch.rsqrt(bn_mod.running_var.float() + bn_mod.eps)
-        scale = gamma.float() * invstd
-        shift = beta.float() - bn_mod.running_mean.float() * scale
-        bn_mod._ibp_folded = (ver, scale, shift)
-        return scale, shift
+        # owned by the module's own running_var, so one entry per BN module
+        var = bn.running_var
+        return versioned(var, "bn-fold",
+                         (gamma._version, bn.running_mean._version,
+                          var._version), _fold_bn, bn)
+    bias = conv.bias
     if bias is not None:
-        return _bias_fold(weight, bias)
+        return versioned(bias, "bias-fold", (bias._version,), _fold_bias, bias)
     return None, None
+
+
+def _fold_bn(_, bn):
+    invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+    scale = bn.weight.float() * invstd
+    return scale, bn.bias.float() - bn.running_mean.float() * scale
+
+
+def _fold_bias(_, bias):
+    return (torch.ones(bias.shape[0], device=bias.device, dtype=torch.float32),
+            bias.detach().float())
 
 
 def _tick_running_stats(bn_mod):
@@ -118,12 +119,9 @@ class ConvBnActFn(torch.autograd.Function):
         x = _to_cl(x)
 
         # inference fast path: fold BN into the conv epilogue -> ONE kernel.
-        # `inference` is computed OUTSIDE apply(): grad mode is always off
-        # inside Function.forward, so torch.is_grad_enabled() can't be used here.
-        if inference and x.dtype == torch.bfloat16:
-            from . import conv_kernels
-            scale, shift = _inference_epilogue(weight, bias, gamma, beta,
-                                               bn_mod)
+        # `inference`, decided OUTSIDE apply(): None or the (scale, shift)
+        if inference is not None:
+            scale, shift = inference
             if scale is not None or act or residual is not None \
                     or residual_post is not None:
                 y = conv_kernels.conv_fwd(x, weight, stride, padding, dilation,
@@ -277,8 +275,9 @@ def conv_bn_act_hip(x, conv, bn, act: bool, residual=None, training: bool = Fals
     nn.Conv2d / nn.BatchNorm2d containers and runs the fused function."""
     gamma = bn.weight if bn is not None else None
     beta = bn.bias if bn is not None else None
-    bn_training = training and (bn is not None and bn.training)
-    inference = not bn_training and not torch.is_grad_enabled()
+    bn_training = _bn_training(bn, training)
+    inference = _inference_epilogue(conv, bn) \
+        if _on_inference_path(x, bn, training) else None
     return ConvBnActFn.apply(
         x, conv.weight, conv.bias, gamma, beta, residual,
         residual_post, residual_post2,
@@ -289,7 +288,6 @@ def conv_bn_act_hip(x, conv, bn, act: bool, residual=None, training: bool = Fals
 def upconv_fold_enabled() -> bool:
     """``IBP_UPCONV_FOLD=0`` (read at call time) restores the separate
     upsample kernel and the 3x3 conv over the upsampled map for A/B runs."""
-    import os
     return os.environ.get("IBP_UPCONV_FOLD", "1") != "0"
 
 
@@ -300,16 +298,10 @@ def upsample_conv_bn_act_hip(low, conv, bn, act: bool, training: bool = False,
     with Cin % 64 == 0 and Cout % 8 == 0 runs as four parity 2x2 convs over
     ``low`` itself (``conv_kernels.upfold_fwd``); everything else runs the
     upsample kernel and the conv as two calls."""
-    bn_training = training and (bn is not None and bn.training)
-    if not bn_training and not torch.is_grad_enabled() \
-            and upconv_fold_enabled():
-        from . import conv_kernels
+    if _on_inference_path(low, bn, training) and upconv_fold_enabled():
         if conv_kernels.upfold_supported(low, conv.weight, conv.stride,
                                          conv.padding, conv.dilation):
-            scale, shift = _inference_epilogue(
-                conv.weight, conv.bias,
-                bn.weight if bn is not None else None,
-                bn.bias if bn is not None else None, bn)
+            scale, shift = _inference_epilogue(conv, bn)
             return conv_kernels.upfold_fwd(
                 _to_cl(low), conv.weight, scale=scale, shift=shift, act=act,
                 residual_post=residual_post, residual_post2=residual_post2)
@@ -322,7 +314,6 @@ def upsample_conv_bn_act_hip(low, conv, bn, act: bool, training: bool = False,
 def conv_group_enabled() -> bool:
     """``IBP_CONV_GROUP=0`` (read at call time) restores one launch per conv
     for A/B runs."""
-    import os
     return os.environ.get("IBP_CONV_GROUP", "1") != "0"
 
 
@@ -335,38 +326,25 @@ def conv_bn_act_group_hip(items):
     mode, every member inside the MFMA envelope); otherwise every member goes
     through :func:`conv_bn_act_hip` on its own. Outputs are bit-identical
     either way: a grouped member runs the plan it would get alone."""
-    def single(it):
-        return conv_bn_act_hip(it["x"], it["conv"], it["bn"], it["act"],
-                               residual=it.get("residual"),
-                               training=it.get("training", False),
-                               residual_post=it.get("residual_post"),
-                               residual_post2=it.get("residual_post2"))
-
-    groupable = len(items) > 1 and conv_group_enabled() \
-        and not torch.is_grad_enabled()
-    members = []
-    if groupable:
-        from . import conv_kernels
+    if len(items) > 1 and conv_group_enabled() and all(
+            _on_inference_path(it["x"], it["bn"], it.get("training", False))
+            for it in items):
+        members = []
         for it in items:
-            bn = it["bn"]
-            if it["x"].dtype != torch.bfloat16 or \
-                    (it.get("training", False) and bn is not None
-                     and bn.training):
-                groupable = False
-                break
             conv = it["conv"]
-            scale, shift = _inference_epilogue(
-                conv.weight, conv.bias,
-                bn.weight if bn is not None else None,
-                bn.bias if bn is not None else None, bn)
+            scale, shift = _inference_epilogue(conv, it["bn"])
             members.append(dict(
                 x=_to_cl(it["x"]), weight=conv.weight, stride=conv.stride,
                 padding=conv.padding, dilation=conv.dilation, scale=scale,
                 shift=shift, residual=it.get("residual"), act=it["act"],
                 residual_post=it.get("residual_post"),
                 residual_post2=it.get("residual_post2")))
-    if groupable:
         ys = conv_kernels.conv_fwd_group(members)
         if ys is not None:
             return ys
-    return [single(it) for it in items]
+    return [conv_bn_act_hip(it["x"], it["conv"], it["bn"], it["act"],
+                            residual=it.get("residual"),
+                            training=it.get("training", False),
+                            residual_post=it.get("residual_post"),
+                            residual_post2=it.get("residual_post2"))
+            for it in items]

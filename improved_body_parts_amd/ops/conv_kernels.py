@@ -4,8 +4,7 @@ The CDNA4 kernels (csrc/conv_mfma.hip) implement NHWC bf16 convolution as an
 implicit GEMM on the bf16 matrix cores:
     C[M=N*Ho*Wo][N=Cout] = A[M][K=KH*KW*Cin] @ B[K][Cout]
 with fwd, dgrad (stride-1: conv with 180-rotated transposed weights) and
-split-K wgrad. Weights are re-packed to [KH*KW*Cin][Cout] (Cout contiguous)
-per forward; the pack is cached against the weight tensor's version counter.
+split-K wgrad. Weight packs are cached against the weight's version counter.
 
 Each entry point returns ``None`` when the shape is outside the kernel's
 envelope, and the caller falls back to the library conv.
@@ -17,45 +16,49 @@ import os
 import torch
 
 from ._backend import hip_extension
+from ._cache import versioned
 
 _CL = torch.channels_last
 
-# shapes supported by the MFMA path: stride-1 any dilation, and stride-2 fwd
 DISABLE = os.environ.get("IBP_AMD_DISABLE_MFMA_CONV") == "1"
 
 
-def _supported(x, weight, stride, padding, dilation, for_grad=False):
+def _supported(x, stride):
     """Envelope of the MFMA kernels: bf16, square stride. Any Cin (subpieces
     crossing filter-tap boundaries — the 7x7 Cin=3 stem — take the kernel's
     per-element gather path), any padding (Ho/Wo are passed explicitly)."""
-    if DISABLE:
-        return False
-    if x.dtype != torch.bfloat16:
-        return False
-    if stride[0] != stride[1]:
-        return False
-    return True
+    return not DISABLE and x.dtype == torch.bfloat16 \
+        and stride[0] == stride[1]
 
 
-import weakref
+def _cl(t):
+    return None if t is None else t.contiguous(memory_format=_CL)
 
-_pack_cache = {}
+
+# epilogue: (scale, shift, residual, act, residual_post, residual_post2)
+_NO_EPI = (None, None, None, False, None, None)
 
 
-def _cached_pack(weight: torch.Tensor, tag: str, pack_fn) -> torch.Tensor:
-    """Cache packs per weight tensor, invalidated by the autograd version
-    counter; a weakref finalizer drops the entry when the weight dies (a bare
-    id() key would alias recycled ids)."""
-    key = (id(weight), tag)
-    entry = _pack_cache.get(key)
-    ver = weight._version
-    if entry is not None and entry[0] == ver:
-        return entry[1]
-    packed = pack_fn(weight.detach().to(torch.bfloat16))
-    if entry is None:
-        weakref.finalize(weight, _pack_cache.pop, key, None)
-    _pack_cache[key] = (ver, packed)
-    return packed
+def _conv_args(x, pack, w_shape, stride, padding, dilation, epi=_NO_EPI,
+               zs=1, out_hw=None):
+    """One conv as the extension's forward entries take it: ``(x, pack, geom,
+    *epi)`` with x and the residuals channels_last and ``geom`` the row ``[N,
+    H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, dil_h, dil_w, Ho, Wo, zs]``.
+    ``w_shape`` is ``(Cout, Cin, KH, KW)`` of the conv that runs, ``epi`` its
+    epilogue in the order of ``_NO_EPI``; ``out_hw`` overrides the output size
+    that follows from the padding (asymmetric pads, dgrad)."""
+    x = x.contiguous(memory_format=_CL)
+    n, cin, h, w_ = x.shape
+    cout, _, kh, kw = w_shape
+    if out_hw is None:
+        out_hw = (
+            (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1,
+            (w_ + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1)
+    geom = [n, h, w_, cin, cout, kh, kw, stride[0], padding[0], padding[1],
+            dilation[0], dilation[1], out_hw[0], out_hw[1], zs]
+    scale, shift, residual, act, residual_post, residual_post2 = epi
+    return (x, pack, geom, scale, shift, _cl(residual), bool(act),
+            _cl(residual_post), _cl(residual_post2))
 
 
 def _pack_pair(weight: torch.Tensor):
@@ -65,18 +68,16 @@ def _pack_pair(weight: torch.Tensor):
     persistent buffers; weights change every optimizer step, so the previous
     per-pack eager flip/permute/reshape chains re-ran ~500 small kernels per
     training step (~1.5% in launch overhead alone)."""
-    key = (id(weight), "pair")
-    entry = _pack_cache.get(key)
-    ver = weight._version
-    if entry is not None and entry[0] == ver:
-        return entry[1], entry[2]
+    return versioned(weight, "pair", (weight._version,), _build_pair, weight)
+
+
+def _build_pair(prev, weight):
     cout, cin, kh, kw = weight.shape
     w = weight.detach()
-    use_kernel = (w.is_cuda and w.dtype == torch.bfloat16
-                  and w.is_contiguous())
+    use_kernel = w.is_cuda and w.dtype == torch.bfloat16 and w.is_contiguous()
     if use_kernel:
-        if entry is not None and entry[3]:
-            fwd_buf, dgr_buf = entry[1], entry[2]
+        if prev is not None and prev[2]:
+            fwd_buf, dgr_buf = prev[0], prev[1]
         else:
             fwd_buf = torch.empty(cout, kh * kw * cin, dtype=torch.bfloat16,
                                   device=w.device)
@@ -88,10 +89,7 @@ def _pack_pair(weight: torch.Tensor):
         fwd_buf = wd.permute(0, 2, 3, 1).reshape(cout, -1).contiguous()
         dgr_buf = torch.flip(wd, dims=(2, 3)).permute(1, 2, 3, 0) \
             .reshape(cin, -1).contiguous()
-    if entry is None:
-        weakref.finalize(weight, _pack_cache.pop, key, None)
-    _pack_cache[key] = (ver, fwd_buf, dgr_buf, use_kernel)
-    return fwd_buf, dgr_buf
+    return fwd_buf, dgr_buf, use_kernel
 
 
 def packed_weight(weight: torch.Tensor) -> torch.Tensor:
@@ -116,8 +114,8 @@ def packed_weight_dgrad(weight: torch.Tensor) -> torch.Tensor:
 # tap-uniform and 16-B vectorizable. Same trick for wgrad; dgrad is never
 # needed (the stem is the input layer).
 
-def _is_stem(x, weight, stride, padding, dilation):
-    return (weight.shape[2] == 7 and weight.shape[3] == 7
+def _is_stem(x, w_shape, stride, padding, dilation):
+    return (w_shape[2] == 7 and w_shape[3] == 7
             and stride[0] == 2 and stride[1] == 2 and x.shape[1] == 3
             and padding[0] == 3 and padding[1] == 3
             and dilation[0] == 1 and dilation[1] == 1
@@ -157,45 +155,39 @@ def _stem_weight_lut(device):
     return lut
 
 
-def _stem_pack_weight(weight):
+def _stem_pack_weight(_, weight):
     """[64,3,7,7] -> packed bf16 [64][K=4*4*16] for the s2d conv."""
-    def pack(w):
-        cout = w.shape[0]
-        wp = torch.zeros(cout, 16, 4, 4, dtype=w.dtype, device=w.device)
-        lut = _stem_weight_lut(w.device)
-        wp.view(cout, -1)[:, lut] = w.reshape(cout, -1)
-        # -> [cout][kh'*kw'*c'] (tap-major, channel fastest) like packed_weight
-        return wp.permute(0, 2, 3, 1).reshape(cout, -1).contiguous()
-    return _cached_pack(weight, "s2d", pack)
+    w = weight.detach().to(torch.bfloat16)
+    cout = w.shape[0]
+    wp = torch.zeros(cout, 16, 4, 4, dtype=w.dtype, device=w.device)
+    wp.view(cout, -1)[:, _stem_weight_lut(w.device)] = w.reshape(cout, -1)
+    # -> [cout][kh'*kw'*c'] (tap-major, channel fastest) like packed_weight
+    return wp.permute(0, 2, 3, 1).reshape(cout, -1).contiguous()
 
 
-def _stem_fwd(x, weight, scale, shift, residual, act,
-              residual_post, residual_post2):
-    ext = hip_extension()
-    s = _stem_s2d_input(x).contiguous(memory_format=_CL)
-    n, _, hs, ws = s.shape
-    cout = weight.shape[0]
-    if residual is not None:
-        residual = residual.contiguous(memory_format=_CL)
-    if residual_post is not None:
-        residual_post = residual_post.contiguous(memory_format=_CL)
-    if residual_post2 is not None:
-        residual_post2 = residual_post2.contiguous(memory_format=_CL)
-    y = ext.conv_mfma_fwd(s, _stem_pack_weight(weight), n, hs, ws, 16, cout,
-                          4, 4, 1, 2, 2, 1, 1, hs, ws,
-                          scale, shift, residual, act,
-                          residual_post, residual_post2, 1)
+def _stem_fwd(x, weight, epi):
+    s = _stem_s2d_input(x)
+    pack = versioned(weight, "s2d", (weight._version,), _stem_pack_weight,
+                     weight)
+    y = hip_extension().conv_mfma_fwd(*_conv_args(
+        s, pack, (weight.shape[0], 16, 4, 4), (1, 1), (2, 2), (1, 1), epi,
+        out_hw=s.shape[2:]))
     return y.permute(0, 3, 1, 2)
 
 
+def _wgrad(x, dy, w_shape, stride, padding, dilation):
+    x, dy = _cl(x), _cl(dy)
+    n, cin, h, w_ = x.shape
+    cout, _, kh, kw = w_shape
+    return hip_extension().conv_mfma_wgrad(
+        x, dy, n, h, w_, cin, cout, kh, kw, stride[0], padding[0], padding[1],
+        dilation[0], dilation[1], dy.shape[2], dy.shape[3])
+
+
 def _stem_wgrad(x, dy, w_shape):
-    ext = hip_extension()
-    s = _stem_s2d_input(x).contiguous(memory_format=_CL)
-    dy = dy.contiguous(memory_format=_CL)
-    n, _, hs, ws = s.shape
     cout = w_shape[0]
-    dwp = ext.conv_mfma_wgrad(s, dy, n, hs, ws, 16, cout, 4, 4,
-                              1, 2, 2, 1, 1, dy.shape[2], dy.shape[3])
+    dwp = _wgrad(_stem_s2d_input(x), dy, (cout, 16, 4, 4), (1, 1), (2, 2),
+                 (1, 1))
     lut = _stem_weight_lut(x.device)
     return dwp.reshape(cout, -1)[:, lut].reshape(cout, 3, 7, 7)
 
@@ -208,30 +200,14 @@ def conv_fwd(x, weight, stride, padding, dilation,
     Conv+BN+LeakyReLU module is ONE kernel on the inference path.
     ``residual_post``/``residual_post2`` are added AFTER the activation (the
     hourglass up1+deconv1 join and the cross-stack feature-cache add)."""
-    if not _supported(x, weight, stride, padding, dilation):
+    if not _supported(x, stride):
         return None
-    ext = hip_extension()
-    if not hasattr(ext, "conv_mfma_fwd"):
-        return None
-    if _is_stem(x, weight, stride, padding, dilation):
-        return _stem_fwd(x, weight, scale, shift, residual, act,
-                         residual_post, residual_post2)
-    x = x.contiguous(memory_format=_CL)
-    n, cin, h, w_ = x.shape
-    cout, _, kh, kw = weight.shape
-    ho = (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    wo = (w_ + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    if residual is not None:
-        residual = residual.contiguous(memory_format=_CL)
-    if residual_post is not None:
-        residual_post = residual_post.contiguous(memory_format=_CL)
-    if residual_post2 is not None:
-        residual_post2 = residual_post2.contiguous(memory_format=_CL)
-    y = ext.conv_mfma_fwd(x, packed_weight(weight), n, h, w_, cin, cout,
-                          kh, kw, stride[0], padding[0], padding[1],
-                          dilation[0], dilation[1], ho, wo,
-                          scale, shift, residual, act,
-                          residual_post, residual_post2, 1)
+    epi = (scale, shift, residual, act, residual_post, residual_post2)
+    if _is_stem(x, weight.shape, stride, padding, dilation):
+        return _stem_fwd(x, weight, epi)
+    y = hip_extension().conv_mfma_fwd(*_conv_args(
+        x, packed_weight(weight), weight.shape, stride, padding, dilation,
+        epi))
     return y.permute(0, 3, 1, 2)  # NHWC buffer -> NCHW view (channels_last)
 
 
@@ -244,34 +220,21 @@ def conv_fwd_group(members):
     single call bit for bit. Returns the outputs in order, or ``None`` when a
     member is outside the grouped envelope (the caller then issues the
     members one by one)."""
-    ext = hip_extension()
-    xs, packs, geom = [], [], []
-    scales, shifts, ress, acts, posts, post2s = [], [], [], [], [], []
+    # one list per argument of conv_mfma_fwd; plain appends (docs/KERNELS.md)
+    cols = [[] for _ in range(9)]
     for m in members:
         x, weight = m["x"], m["weight"]
         stride, padding, dilation = m["stride"], m["padding"], m["dilation"]
-        if not _supported(x, weight, stride, padding, dilation) \
-                or _is_stem(x, weight, stride, padding, dilation):
+        if not _supported(x, stride) \
+                or _is_stem(x, weight.shape, stride, padding, dilation):
             return None
-        x = x.contiguous(memory_format=_CL)
-        n, cin, h, w_ = x.shape
-        cout, _, kh, kw = weight.shape
-        ho = (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-        wo = (w_ + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-        xs.append(x)
-        packs.append(packed_weight(weight))
-        geom.append([n, h, w_, cin, cout, kh, kw, stride[0], padding[0],
-                     padding[1], dilation[0], dilation[1], ho, wo, 1])
-        scales.append(m.get("scale"))
-        shifts.append(m.get("shift"))
-        acts.append(1 if m.get("act") else 0)
-        for lst, key in ((ress, "residual"), (posts, "residual_post"),
-                         (post2s, "residual_post2")):
-            r = m.get(key)
-            lst.append(r.contiguous(memory_format=_CL) if r is not None
-                       else None)
-    ys = ext.conv_mfma_fwd_grouped(xs, packs, geom, scales, shifts, ress,
-                                   acts, posts, post2s)
+        row = _conv_args(
+            x, packed_weight(weight), weight.shape, stride, padding, dilation,
+            (m.get("scale"), m.get("shift"), m.get("residual"), m.get("act"),
+             m.get("residual_post"), m.get("residual_post2")))
+        for col, v in zip(cols, row):
+            col.append(v)
+    ys = hip_extension().conv_mfma_fwd_grouped(*cols)
     return [y.permute(0, 3, 1, 2) for y in ys]
 
 
@@ -316,15 +279,19 @@ def upfold_weight_reference(weight: torch.Tensor) -> torch.Tensor:
 def upfold_packed_weight(weight: torch.Tensor) -> torch.Tensor:
     """bf16 [4][Cout][4*Cin] folded packs of a 3x3 weight, one
     ``pack_upfold_weight_kernel`` launch per weight version."""
-    def pack(w):
-        cout, cin = w.shape[:2]
-        if w.is_cuda:
-            out = torch.empty(4, cout, 4 * cin, dtype=torch.bfloat16,
-                              device=w.device)
-            hip_extension().pack_upfold_weight(w.contiguous(), out)
-            return out
-        return upfold_weight_reference(w).reshape(4, cout, 4 * cin)
-    return _cached_pack(weight, "upfold", pack)
+    return versioned(weight, "upfold", (weight._version,), _upfold_pack,
+                     weight)
+
+
+def _upfold_pack(_, weight):
+    w = weight.detach().to(torch.bfloat16)
+    cout, cin = w.shape[:2]
+    if w.is_cuda:
+        out = torch.empty(4, cout, 4 * cin, dtype=torch.bfloat16,
+                          device=w.device)
+        hip_extension().pack_upfold_weight(w.contiguous(), out)
+        return out
+    return upfold_weight_reference(w).reshape(4, cout, 4 * cin)
 
 
 def upfold_supported(x, weight, stride, padding, dilation) -> bool:
@@ -344,42 +311,38 @@ def upfold_fwd(x_low, weight, scale=None, shift=None, act=False,
     upsampled tensor: four parity 2x2 convs in one grouped launch, each
     storing its own pixels of the full-resolution output. The folded weights
     carry one more bf16 rounding than the 3x3 pack (docs/KERNELS.md)."""
-    ext = hip_extension()
-    x = x_low.contiguous(memory_format=_CL)
+    x = _cl(x_low)
     n, cin, h, w_ = x.shape
     cout = weight.shape[0]
-    post = [None, None]
-    for i, r in enumerate((residual_post, residual_post2)):
+    post = []
+    for r in (residual_post, residual_post2):
         if r is not None:
             assert tuple(r.shape) == (n, cout, 2 * h, 2 * w_), \
                 f"residual {tuple(r.shape)} is not the upsampled output shape"
-            post[i] = r.contiguous(memory_format=_CL).permute(0, 2, 3, 1)
-    y = ext.conv_mfma_upfold_fwd(x.permute(0, 2, 3, 1),
-                                 upfold_packed_weight(weight), n, h, w_, cin,
-                                 cout, scale, shift, act, post[0], post[1])
+            r = _cl(r).permute(0, 2, 3, 1)
+        post.append(r)
+    # the layer's geometry row: H x W is the low resolution, Ho x Wo twice it
+    geom = [n, h, w_, cin, cout, 3, 3, 1, 1, 1, 1, 1, 2 * h, 2 * w_, 1]
+    y = hip_extension().conv_mfma_upfold_fwd(
+        x.permute(0, 2, 3, 1), upfold_packed_weight(weight), geom, scale,
+        shift, act, *post)
     return y.permute(0, 3, 1, 2)
 
 
 def conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
     """dx = stride-1 conv of the (virtually) zero-dilated dy with 180-rotated
     transposed weights; pad' = dil*(K-1) - pad, gather stride zs = stride."""
-    if not _supported(dy, weight, stride, padding, dilation, for_grad=True):
+    if not _supported(dy, stride):
         return None
-    ext = hip_extension()
-    if not hasattr(ext, "conv_mfma_fwd"):
+    cout, _, kh, kw = weight.shape
+    pad = (dilation[0] * (kh - 1) - padding[0],
+           dilation[1] * (kw - 1) - padding[1])
+    if pad[0] < 0 or pad[1] < 0:
         return None
-    dy = dy.contiguous(memory_format=_CL)
-    n, cout, h, w_ = dy.shape
-    cin, hx, wx = x_shape[1], x_shape[2], x_shape[3]
-    kh, kw = weight.shape[2], weight.shape[3]
-    pad_h = dilation[0] * (kh - 1) - padding[0]
-    pad_w = dilation[1] * (kw - 1) - padding[1]
-    if pad_h < 0 or pad_w < 0:
-        return None
-    dx = ext.conv_mfma_fwd(dy, packed_weight_dgrad(weight), n, h, w_, cout, cin,
-                           kh, kw, 1, pad_h, pad_w,
-                           dilation[0], dilation[1], hx, wx,
-                           None, None, None, False, None, None, stride[0])
+    # the conv that runs maps dy's Cout channels to x's Cin
+    dx = hip_extension().conv_mfma_fwd(*_conv_args(
+        dy, packed_weight_dgrad(weight), (x_shape[1], cout, kh, kw), (1, 1),
+        pad, dilation, zs=stride[0], out_hw=x_shape[2:]))
     return dx.permute(0, 3, 1, 2)
 
 
@@ -392,22 +355,8 @@ def conv_wgrad(x, dy, w_shape, stride, padding, dilation):
     transpose read ``ds_read_b64_tr_b16`` (round 1 left this on MIOpen
     igemm_wrw; the builtin ``__builtin_amdgcn_ds_read_tr16_b64_v4i16``
     makes the layout tractable). Any KHxKW/stride/dilation; bf16 only."""
-    if DISABLE or x.dtype != torch.bfloat16 or dy.dtype != torch.bfloat16:
+    if not _supported(x, stride) or dy.dtype != torch.bfloat16:
         return None
-    if stride[0] != stride[1]:
-        return None
-    ext = hip_extension()
-    if not hasattr(ext, "conv_mfma_wgrad"):
-        return None
-    if w_shape[2] == 7 and w_shape[3] == 7 and x.shape[1] == 3 \
-            and stride[0] == 2 and padding[0] == 3 and dilation[0] == 1 \
-            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0:
+    if _is_stem(x, w_shape, stride, padding, dilation):
         return _stem_wgrad(x, dy, w_shape)
-    x = x.contiguous(memory_format=_CL)
-    dy = dy.contiguous(memory_format=_CL)
-    n, cin, h, w_ = x.shape
-    cout, _, kh, kw = w_shape
-    ho, wo = dy.shape[2], dy.shape[3]
-    return ext.conv_mfma_wgrad(x, dy, n, h, w_, cin, cout, kh, kw,
-                               stride[0], padding[0], padding[1],
-                               dilation[0], dilation[1], ho, wo)
+    return _wgrad(x, dy, w_shape, stride, padding, dilation)

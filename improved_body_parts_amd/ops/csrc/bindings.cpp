@@ -58,15 +58,14 @@ Tensor focal_l2_bwd(const Tensor& pred, const Tensor& gt, const Tensor& mask,
                     double alpha, double beta);
 
 // conv_mfma.hip
-Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
-                     int64_t H, int64_t W, int64_t Cin, int64_t Cout,
-                     int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
-                     int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
-                     int64_t Wo, const c10::optional<Tensor>& scale,
+// geom = N H W Cin Cout KH KW stride pad_h pad_w dil_h dil_w Ho Wo zs
+Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed,
+                     const std::vector<int64_t>& geom,
+                     const c10::optional<Tensor>& scale,
                      const c10::optional<Tensor>& shift,
                      const c10::optional<Tensor>& residual, bool act,
                      const c10::optional<Tensor>& residual_post,
-                     const c10::optional<Tensor>& residual_post2, int64_t zs);
+                     const c10::optional<Tensor>& residual_post2);
 
 std::vector<Tensor> conv_mfma_fwd_grouped(
     const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
@@ -74,7 +73,7 @@ std::vector<Tensor> conv_mfma_fwd_grouped(
     const std::vector<c10::optional<Tensor>>& scales,
     const std::vector<c10::optional<Tensor>>& shifts,
     const std::vector<c10::optional<Tensor>>& residuals,
-    const std::vector<int64_t>& acts,
+    const std::vector<bool>& acts,
     const std::vector<c10::optional<Tensor>>& residual_posts,
     const std::vector<c10::optional<Tensor>>& residual_post2s);
 
@@ -85,8 +84,8 @@ void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
 
 void pack_upfold_weight(const Tensor& w, Tensor& out);
 Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
-                            int64_t N, int64_t H, int64_t W, int64_t Cin,
-                            int64_t Cout, const c10::optional<Tensor>& scale,
+                            const std::vector<int64_t>& geom,
+                            const c10::optional<Tensor>& scale,
                             const c10::optional<Tensor>& shift, bool act,
                             const c10::optional<Tensor>& residual_post,
                             const c10::optional<Tensor>& residual_post2);
@@ -160,14 +159,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("focal_l2_fwd", &focal_l2_fwd);
   m.def("focal_l2_bwd", &focal_l2_bwd);
   m.def("conv_mfma_fwd", &conv_mfma_fwd, "MFMA implicit-GEMM conv forward",
-        py::arg("x"), py::arg("w_packed"), py::arg("N"), py::arg("H"),
-        py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("KH"),
-        py::arg("KW"), py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"),
-        py::arg("dil_h"), py::arg("dil_w"), py::arg("Ho"), py::arg("Wo"),
+        py::arg("x"), py::arg("w_packed"), py::arg("geom"),
         py::arg("scale") = c10::nullopt, py::arg("shift") = c10::nullopt,
         py::arg("residual") = c10::nullopt, py::arg("act") = false,
         py::arg("residual_post") = c10::nullopt,
-        py::arg("residual_post2") = c10::nullopt, py::arg("zs") = 1);
+        py::arg("residual_post2") = c10::nullopt);
   m.def("conv_mfma_fwd_grouped", &conv_mfma_fwd_grouped,
         "independent MFMA convs in one grouped launch per 8 (+ one combine)",
         py::arg("xs"), py::arg("ws_packed"), py::arg("geom"),
@@ -187,8 +183,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_mfma_upfold_fwd", &conv_mfma_upfold_fwd,
         "conv3x3(nearest_x2(x_low)) + epilogue as four parity 2x2 convs in "
         "one grouped launch",
-        py::arg("x_low"), py::arg("packs"), py::arg("N"), py::arg("H"),
-        py::arg("W"), py::arg("Cin"), py::arg("Cout"),
+        py::arg("x_low"), py::arg("packs"), py::arg("geom"),
         py::arg("scale") = c10::nullopt, py::arg("shift") = c10::nullopt,
         py::arg("act") = false, py::arg("residual_post") = c10::nullopt,
         py::arg("residual_post2") = c10::nullopt);

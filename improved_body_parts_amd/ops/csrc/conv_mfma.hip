@@ -37,11 +37,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <algorithm>
-#include <cstddef>
-#include <cstdlib>
 #include <type_traits>
 #include <vector>
 #include "common.h"
+#include "conv_params.h"   // ConvParams and the launch tables
+#include "conv_plan.h"     // the host planner
 
 namespace ibp {
 
@@ -50,35 +50,6 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef unsigned short ushortv8 __attribute__((ext_vector_type(8)));
 typedef unsigned short ushortv4 __attribute__((ext_vector_type(4)));
-
-constexpr int BK = 64;        // K depth per step
-
-struct ConvParams {
-  const unsigned short* x;   // NHWC bf16
-  const unsigned short* w;   // [Cout][K] bf16 (N-major pack)
-  unsigned short* y;         // NHWC bf16 out
-  const float* scale;        // optional per-channel scale (folded BN)
-  const float* shift;        // optional per-channel shift / bias
-  const unsigned short* res;      // optional residual, added BEFORE act
-  const unsigned short* res_post; // optional residual, added AFTER act
-  const unsigned short* res_post2;
-  int N, H, W, Cin, Cout, KH, KW;
-  int stride, pad_h, pad_w, dil_h, dil_w, Ho, Wo;
-  int zs;                    // gather stride (transposed-conv dgrad), 1 = off
-  long long M;               // N*Ho*Wo
-  int K;                     // KH*KW*Cin
-  int n_mtiles;              // ceil(M/BM)
-  int act;                   // leaky-relu on epilogue
-  int splitk;                // K-dimension split factor (small-grid layers)
-  float* ws;                 // fp32 workspace for split-K partial accumulation
-  int vec_epi;               // 1: 4-channel epilogue groups, 2: 8-channel
-  int pair_epi;              // fallback may use 2-channel (4-byte) accesses
-  int m32;                   // M (+ tile padding) fits 32-bit index math
-  // output scatter (nearest-x2 upsample folded into the conv): rows index the
-  // LOW-resolution Ho x Wo grid and row (n, i, j) is stored at pixel
-  // (n*2Ho + 2i+py)*2Wo + 2j+px of y / res / res_post / res_post2
-  int up, py, px;
-};
 
 // LDS tile addressing: unpadded BK-short rows with a T2 XOR swizzle — the
 // 16-lane ds_read_b128 group (16 distinct rows, same k-slice) spreads over 8
@@ -603,21 +574,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
 // problem would get alone, with a problem-local block id. Every block writes
 // only its own problem's outputs, so the order of problems in the grid never
 // changes a result; the host puts the blocks with the most K-chunks first.
-constexpr int kMaxGroup = 8;
-
-struct ConvGroupParams {
-  ConvParams p[kMaxGroup];
-  int block_end[kMaxGroup];
-  int cfg[kMaxGroup];        // tile_cfg(BM, BN, deep)
-  int n;
-};
-
-// tile configuration index shared by host and device
-constexpr int tile_cfg(int BM, int BN, bool deep) {
-  return ((BM == 128 ? (BN == 128 ? 0 : 1) : (BM == 64 ? 2 : 3)) << 1) |
-         (deep ? 1 : 0);
-}
-
+//
 // <true> is the upfold launch: every problem is one output parity of a
 // nearest-x2-upsample-folded conv and scatters its rows (ConvParams::up).
 template <bool UP>
@@ -670,20 +627,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
 // The grouped kernel reads its table at offset 0 of the kernel-argument
 // segment: it must stay the kernel's ONLY explicit argument (explicit
 // arguments come first in the segment, hidden ones after), with the problem
-// array leading the struct.
+// array leading the struct (asserted in conv_params.h).
 static_assert(std::is_same<decltype(&conv_mfma_grouped_kernel<false>),
                            void (*)(ConvGroupParams)>::value &&
                   std::is_same<decltype(&conv_mfma_grouped_kernel<true>),
                                void (*)(ConvGroupParams)>::value,
               "conv_mfma_grouped_kernel must take the table as its only "
               "argument: it is read at kernarg offset 0");
-static_assert(offsetof(ConvGroupParams, p) == 0 &&
-                  std::is_standard_layout<ConvGroupParams>::value &&
-                  std::is_trivially_copyable<ConvGroupParams>::value &&
-                  sizeof(ConvParams) % alignof(ConvParams) == 0 &&
-                  sizeof(ConvGroupParams) <= 4096,
-              "ConvGroupParams layout: problem array first, within the "
-              "kernel-argument limit");
 
 // One output element of the split-K combine; slices summed s = 0..splitk-1
 // from 0.f so the bits do not depend on which path ran.
@@ -710,10 +660,6 @@ __device__ __forceinline__ float combine_one(float v, float sc, float sh,
 // Output scatter (ConvParams::up): the slabs are in the problem's row order,
 // y and the residuals are addressed at the row's full-resolution pixel. The
 // host sets `up` only when the row count fits 32 bits.
-struct OutScatter {
-  int up, py, px, Ho, Wo;
-};
-
 __device__ __forceinline__ long long scatter_pixel(unsigned m,
                                                    const OutScatter& s) {
   const unsigned j = m % (unsigned)s.Wo; m /= (unsigned)s.Wo;
@@ -819,25 +765,6 @@ __global__ void splitk_combine_kernel(const float* __restrict__ ws,
 // grouped combine: the split members of one grouped conv launch, same
 // block -> problem table scheme; each problem keeps the grid size and the
 // <VEC> arithmetic it has alone.
-struct CombineProblem {
-  const float* ws;
-  unsigned short* y;
-  const float* scale;
-  const float* shift;
-  const unsigned short* res;
-  const unsigned short* res_post;
-  const unsigned short* res_post2;
-  long long total;
-  int C, act, splitk, vec;
-  OutScatter os;
-};
-
-struct CombineGroupParams {
-  CombineProblem c[kMaxGroup];
-  int block_end[kMaxGroup];
-  int n;
-};
-
 template <bool UP>
 __global__ void splitk_combine_grouped_kernel(CombineGroupParams g) {
   const int gb = blockIdx.x;
@@ -922,10 +849,13 @@ __global__ void pack_weight_kernel(const unsigned short* __restrict__ w,
 }  // namespace ibp
 
 // ===========================================================================
+// Host side: tensors -> ConvProblem, outputs and workspaces, launches. What
+// runs is decided in conv_plan.h (checked on the CPU, test_conv_plan_cpu.py).
 using torch::Tensor;
+using OptTensor = c10::optional<Tensor>;
 
 void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
-                      const c10::optional<Tensor>& dgrad_pack) {
+                      const OptTensor& dgrad_pack) {
   TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
               w.scalar_type() == at::ScalarType::BFloat16);
   int Cout = (int)w.size(0), Cin = (int)w.size(1);
@@ -942,402 +872,6 @@ void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
       Cout, Cin, KH, KW);
 }
 
-namespace {
-
-// Everything conv_mfma_fwd decides before launching: the filled ConvParams
-// (all but the workspace pointer), the tile, the split and the epilogue
-// paths. The single and the grouped entry both launch from this plan, so a
-// member of a group runs exactly what it would run alone.
-struct ConvPlan {
-  ibp::ConvParams p;
-  Tensor y;
-  int BM, BN;
-  bool deep;
-  bool vec_combine;    // before the workspace is known: all BUT its alignment
-  int nblocks;         // ntiles * splitk
-  int nk_block;        // K-chunks per block
-  long long ws_elems;  // fp32 workspace elements (0 when unsplit)
-};
-
-bool misaligned(const void* ptr, uintptr_t a) {
-  return ptr != nullptr && (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) != 0;
-}
-
-// Tile and split-K choice: a function of the GEMM extents alone (and the
-// IBP_CONV_BM / IBP_SPLITK_TARGET overrides), so it can be queried without
-// tensors (conv_mfma_tile_plan below, used by the tests).
-struct TilePlan {
-  int BM, BN, n_mtiles, ntiles, splitk, nk_block;
-  bool deep;
-};
-
-// BM x BN for a GEMM with M rows
-void pick_tile(long long M, int Cout, int& BM_out, int& BN_out) {
-  // ---- tile selection -------------------------------------------------------
-  // BM: small-M tiles for the hourglass's 8^2/16^2 scales (avoids the 8-16x
-  // split-K workspace round-trip measured in round 1); BN: minimise padded
-  // cols (Cout=192 as 3x64 beats 2x128 — half the second 128-tile is wasted).
-  int BM = 128;
-  if (M <= 2048) BM = 32;
-  else if (M <= 8192) BM = 64;
-  if (const char* e = getenv("IBP_CONV_BM")) BM = atoi(e);
-  const long long padded128 = ((Cout + 127) / 128) * 128LL;
-  const long long padded64 = ((Cout + 63) / 64) * 64LL;
-  int BN = (BM == 128 && Cout > 64 && padded128 <= padded64) ? 128 : 64;
-  BM_out = BM;
-  BN_out = BN;
-}
-
-// split-K factor for a grid of `ntiles` output tiles over nk_total K-chunks
-int pick_split(int ntiles, int nk_total) {
-  // split K on small grids so the 256-CU chip stays filled (~2 blocks/CU).
-  // Normalise so EVERY slice has work: with raw splitk=7 over nk_total=8 the
-  // last 3 slices get no chunks, return early, and the combine kernel then
-  // sums their UNINITIALISED workspace slices (silent garbage whenever the
-  // allocator hands back dirty memory — found as exploding gradients through
-  // the scale-2 Merge convs, scripts/diag_splitk.py).
-  int sk_target = 384;
-  if (const char* e = getenv("IBP_SPLITK_TARGET")) sk_target = atoi(e);
-  int splitk = 1;
-  if (ntiles < sk_target && nk_total > 1) {
-    splitk = std::min((int)nk_total, (sk_target + ntiles - 1) / ntiles);
-    int nk_chunk = ((int)nk_total + splitk - 1) / splitk;
-    splitk = ((int)nk_total + nk_chunk - 1) / nk_chunk;
-  }
-  return splitk;
-}
-
-TilePlan plan_tile(long long M, int Cout, int K) {
-  TilePlan t;
-  int BM, BN;
-  pick_tile(M, Cout, BM, BN);
-  t.n_mtiles = (int)((M + BM - 1) / BM);
-  const int ntiles = t.n_mtiles * (int)((Cout + BN - 1) / BN);
-  const int nk_total = (K + ibp::BK - 1) / ibp::BK;
-  const int splitk = pick_split(ntiles, nk_total);
-  t.BM = BM;
-  t.BN = BN;
-  t.ntiles = ntiles;
-  t.splitk = splitk;
-  // short-K blocks (the 1x1 layers: <= 6 chunks) never reach pipeline
-  // steady state with single-stage prefetch — use the 2-deep variant there
-  t.nk_block = (nk_total + splitk - 1) / splitk;
-  t.deep = t.nk_block <= 6;
-  return t;
-}
-
-// One output parity of an upsample-folded conv (see conv_mfma_upfold_fwd):
-// the caller provides the shared full-resolution output, the weight slice of
-// this parity and the tile/split chosen for the four parities together.
-struct UpFold {
-  Tensor y;                  // [N, 2H, 2W, Cout]
-  const unsigned short* w;   // this parity's [Cout][4*Cin] pack
-  int py, px;
-  TilePlan t;
-};
-
-ConvPlan plan_conv(const Tensor& x, const Tensor& w_packed, int64_t N,
-                   int64_t H, int64_t W, int64_t Cin, int64_t Cout,
-                   int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
-                   int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
-                   int64_t Wo, const c10::optional<Tensor>& scale,
-                   const c10::optional<Tensor>& shift,
-                   const c10::optional<Tensor>& residual, bool act,
-                   const c10::optional<Tensor>& residual_post,
-                   const c10::optional<Tensor>& residual_post2, int64_t zs,
-                   const UpFold* up = nullptr) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::ScalarType::BFloat16);
-  TORCH_CHECK(w_packed.is_contiguous());
-  ConvPlan plan;
-  ibp::ConvParams& p = plan.p;
-  p.x = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  p.w = reinterpret_cast<const unsigned short*>(w_packed.data_ptr());
-  p.scale = scale.has_value() ? scale->data_ptr<float>() : nullptr;
-  p.shift = shift.has_value() ? shift->data_ptr<float>() : nullptr;
-  p.res = residual.has_value()
-              ? reinterpret_cast<const unsigned short*>(residual->data_ptr())
-              : nullptr;
-  p.res_post =
-      residual_post.has_value()
-          ? reinterpret_cast<const unsigned short*>(residual_post->data_ptr())
-          : nullptr;
-  p.res_post2 =
-      residual_post2.has_value()
-          ? reinterpret_cast<const unsigned short*>(residual_post2->data_ptr())
-          : nullptr;
-  p.N = (int)N; p.H = (int)H; p.W = (int)W; p.Cin = (int)Cin;
-  p.Cout = (int)Cout; p.KH = (int)KH; p.KW = (int)KW;
-  p.stride = (int)stride; p.pad_h = (int)pad_h; p.pad_w = (int)pad_w;
-  p.dil_h = (int)dil_h; p.dil_w = (int)dil_w; p.Ho = (int)Ho; p.Wo = (int)Wo;
-  p.zs = (int)zs;
-  p.M = (long long)N * Ho * Wo;
-  p.K = (int)(KH * KW * Cin);
-  p.act = act ? 1 : 0;
-  // any Cin is legal: subpieces crossing tap boundaries take the per-element
-  // re-derive path (the Cin=3 stem runs there; Cin % 8 == 0 stays vectorized)
-  plan.y = up ? up->y : torch::empty({N, Ho, Wo, Cout}, x.options());
-  p.y = reinterpret_cast<unsigned short*>(plan.y.data_ptr());
-  p.up = up ? 1 : 0;
-  p.py = up ? up->py : 0;
-  p.px = up ? up->px : 0;
-  if (up) p.w = up->w;
-
-  const TilePlan t = up ? up->t : plan_tile(p.M, p.Cout, p.K);
-  const int BM = t.BM, BN = t.BN, splitk = t.splitk;
-  p.n_mtiles = t.n_mtiles;
-  p.splitk = splitk;
-  // per-split slices written with plain stores -> an uninitialised workspace
-  // is safe (every in-range element is covered by every split's epilogue)
-  plan.ws_elems = splitk > 1 ? (long long)splitk * p.M * Cout : 0;
-  p.ws = nullptr;
-  // vector epilogue: 4-channel groups need Cout % 4 == 0 (then y, freshly
-  // allocated, and the fp32 slabs are 8-/16-byte aligned at every group) plus
-  // 16-byte scale/shift and 8-byte residual pointers on the unsplit path.
-  // The combine's 8-channel groups need Cout % 8 == 0 and 16 bytes throughout.
-  p.vec_epi = Cout % 4 == 0 &&
-              (splitk > 1 ||
-               !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
-                 misaligned(p.res, 8) || misaligned(p.res_post, 8) ||
-                 misaligned(p.res_post2, 8) || misaligned(p.y, 8)));
-  if (p.vec_epi && Cout % 8 == 0 && !misaligned(p.y, 16)) p.vec_epi = 2;
-  p.pair_epi = Cout % 2 == 0 &&
-               !(misaligned(p.res, 4) || misaligned(p.res_post, 4) ||
-                 misaligned(p.res_post2, 4) || misaligned(p.y, 4));
-  plan.vec_combine =
-      Cout % 8 == 0 &&
-      !(misaligned(p.scale, 16) || misaligned(p.shift, 16) ||
-        misaligned(p.res, 16) || misaligned(p.res_post, 16) ||
-        misaligned(p.res_post2, 16) || misaligned(p.y, 16));
-  p.m32 = p.M + BM < (1LL << 31);
-  // the scatter decomposes rows and output pixels' rows in 32-bit math
-  TORCH_CHECK(!up || 4 * p.M + 4 * BM < (1LL << 31),
-              "upfold conv: output too large for 32-bit row math");
-  plan.BM = BM;
-  plan.BN = BN;
-  plan.nblocks = t.ntiles * splitk;
-  plan.nk_block = t.nk_block;
-  plan.deep = t.deep;
-  return plan;
-}
-
-// the workspace pointer completes a plan (its alignment gates vec_combine)
-void set_workspace(ConvPlan& plan, float* ws) {
-  plan.p.ws = ws;
-  plan.vec_combine = plan.vec_combine && !misaligned(ws, 16);
-}
-
-ibp::OutScatter out_scatter(const ibp::ConvParams& p) {
-  return ibp::OutScatter{p.up, p.py, p.px, p.Ho, p.Wo};
-}
-
-int combine_blocks(const ConvPlan& plan) {
-  const long long total = plan.p.M * plan.p.Cout;
-  return ibp::grid_1d(plan.vec_combine ? total / 8 : total, 256, 4096);
-}
-
-void launch_single(const ConvPlan& plan, hipStream_t stream) {
-  const ibp::ConvParams& p = plan.p;
-  TORCH_CHECK(!p.up, "upfold plans launch through launch_group");
-  dim3 grid(plan.nblocks), block(256);
-  const int BM = plan.BM, BN = plan.BN;
-  const bool deep = plan.deep;
-  if (BM == 128 && BN == 128) {
-    if (deep)
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<128, 128, true>), grid, block, 0, stream, p);
-    else
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<128, 128>), grid, block, 0, stream, p);
-  } else if (BM == 128) {
-    if (deep)
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<128, 64, true>), grid, block, 0, stream, p);
-    else
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<128, 64>), grid, block, 0, stream, p);
-  } else if (BM == 64) {
-    if (deep)
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<64, 64, true>), grid, block, 0, stream, p);
-    else
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<64, 64>), grid, block, 0, stream, p);
-  } else {
-    if (deep)
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<32, 64, true>), grid, block, 0, stream, p);
-    else
-      hipLaunchKernelGGL((ibp::conv_mfma_kernel<32, 64>), grid, block, 0, stream, p);
-  }
-  if (p.splitk > 1) {
-    long long total = (long long)p.M * p.Cout;
-    dim3 cblock(256), cgrid(combine_blocks(plan));
-    if (plan.vec_combine) {
-      hipLaunchKernelGGL(ibp::splitk_combine_kernel<true>, cgrid, cblock, 0,
-                         stream, p.ws, p.y, p.scale, p.shift, p.res,
-                         p.res_post, p.res_post2, total, p.Cout, p.act,
-                         p.splitk);
-    } else {
-      hipLaunchKernelGGL(ibp::splitk_combine_kernel<false>, cgrid, cblock, 0,
-                         stream, p.ws, p.y, p.scale, p.shift, p.res,
-                         p.res_post, p.res_post2, total, p.Cout, p.act,
-                         p.splitk);
-    }
-  }
-}
-
-// one grouped conv launch (+ one grouped combine) over plans[first, last)
-void launch_group(std::vector<ConvPlan>& plans, size_t first, size_t last,
-                  const at::TensorOptions& f32, hipStream_t stream,
-                  std::vector<Tensor>& keep) {
-  const int n = (int)(last - first);
-  // one workspace for all split members, 16-byte-aligned sub-allocations
-  long long ws_total = 0;
-  std::vector<long long> ws_off(n, 0);
-  for (int i = 0; i < n; ++i) {
-    ws_off[i] = ws_total;
-    ws_total += (plans[first + i].ws_elems + 3) / 4 * 4;
-  }
-  if (ws_total > 0) {
-    Tensor ws = torch::empty({ws_total}, f32);
-    keep.push_back(ws);
-    for (int i = 0; i < n; ++i)
-      if (plans[first + i].ws_elems > 0)
-        set_workspace(plans[first + i], ws.data_ptr<float>() + ws_off[i]);
-  }
-  // blocks with the most K-chunks first; ties keep list order (deterministic)
-  std::vector<int> order(n);
-  for (int i = 0; i < n; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    return plans[first + a].nk_block > plans[first + b].nk_block;
-  });
-  ibp::ConvGroupParams g{};
-  ibp::CombineGroupParams cg{};
-  int blocks = 0, cblocks = 0, nc = 0;
-  for (int i = 0; i < ibp::kMaxGroup; ++i) {
-    const ConvPlan& plan = plans[first + order[i < n ? i : n - 1]];
-    if (i < n) blocks += plan.nblocks;
-    g.p[i] = plan.p;
-    g.cfg[i] = ibp::tile_cfg(plan.BM, plan.BN, plan.deep);
-    g.block_end[i] = blocks;
-  }
-  g.n = n;
-  for (int i = 0; i < n; ++i) {
-    const ConvPlan& plan = plans[first + order[i]];
-    if (plan.p.splitk <= 1) continue;
-    const ibp::ConvParams& p = plan.p;
-    cblocks += combine_blocks(plan);
-    cg.c[nc] = ibp::CombineProblem{p.ws, p.y, p.scale, p.shift, p.res,
-                                   p.res_post, p.res_post2,
-                                   (long long)p.M * p.Cout, p.Cout, p.act,
-                                   p.splitk, plan.vec_combine ? 1 : 0,
-                                   out_scatter(p)};
-    cg.block_end[nc] = cblocks;
-    ++nc;
-  }
-  for (int i = nc; i < ibp::kMaxGroup; ++i) {
-    cg.c[i] = cg.c[nc > 0 ? nc - 1 : 0];
-    cg.block_end[i] = cblocks;
-  }
-  cg.n = nc;
-  // all members scatter (the four parities of an upfold conv) or none does
-  const bool up = plans[first].p.up != 0;
-  for (int i = 0; i < n; ++i)
-    TORCH_CHECK((plans[first + i].p.up != 0) == up,
-                "grouped conv: upfold and plain members cannot mix");
-  if (up)
-    hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel<true>, dim3(blocks),
-                       dim3(256), 0, stream, g);
-  else
-    hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel<false>, dim3(blocks),
-                       dim3(256), 0, stream, g);
-  if (nc > 0 && up)
-    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel<true>, dim3(cblocks),
-                       dim3(256), 0, stream, cg);
-  else if (nc > 0)
-    hipLaunchKernelGGL(ibp::splitk_combine_grouped_kernel<false>,
-                       dim3(cblocks), dim3(256), 0, stream, cg);
-}
-
-}  // namespace
-
-Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed, int64_t N,
-                     int64_t H, int64_t W, int64_t Cin, int64_t Cout,
-                     int64_t KH, int64_t KW, int64_t stride, int64_t pad_h,
-                     int64_t pad_w, int64_t dil_h, int64_t dil_w, int64_t Ho,
-                     int64_t Wo, const c10::optional<Tensor>& scale,
-                     const c10::optional<Tensor>& shift,
-                     const c10::optional<Tensor>& residual, bool act,
-                     const c10::optional<Tensor>& residual_post,
-                     const c10::optional<Tensor>& residual_post2, int64_t zs) {
-  ConvPlan plan = plan_conv(x, w_packed, N, H, W, Cin, Cout, KH, KW, stride,
-                            pad_h, pad_w, dil_h, dil_w, Ho, Wo, scale, shift,
-                            residual, act, residual_post, residual_post2, zs);
-  Tensor ws;
-  if (plan.ws_elems > 0) {
-    ws = torch::empty({plan.ws_elems}, x.options().dtype(torch::kFloat32));
-    set_workspace(plan, ws.data_ptr<float>());
-  }
-  launch_single(plan, at::hip::getCurrentHIPStream().stream());
-  return plan.y;
-}
-
-// Several independent convs in as few launches as possible: lists of the
-// conv_mfma_fwd arguments (geom[i] = {N, H, W, Cin, Cout, KH, KW, stride,
-// pad_h, pad_w, dil_h, dil_w, Ho, Wo, zs}), outputs in list order. Every
-// member keeps the plan it gets alone — same tile, split, epilogue path and
-// summation order — so each output is bit-identical to the single call.
-std::vector<Tensor> conv_mfma_fwd_grouped(
-    const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
-    const std::vector<std::vector<int64_t>>& geom,
-    const std::vector<c10::optional<Tensor>>& scales,
-    const std::vector<c10::optional<Tensor>>& shifts,
-    const std::vector<c10::optional<Tensor>>& residuals,
-    const std::vector<int64_t>& acts,
-    const std::vector<c10::optional<Tensor>>& residual_posts,
-    const std::vector<c10::optional<Tensor>>& residual_post2s) {
-  const size_t n = xs.size();
-  TORCH_CHECK(n > 0 && ws_packed.size() == n && geom.size() == n &&
-              scales.size() == n && shifts.size() == n &&
-              residuals.size() == n && acts.size() == n &&
-              residual_posts.size() == n && residual_post2s.size() == n,
-              "conv_mfma_fwd_grouped: argument lists differ in length");
-  std::vector<ConvPlan> plans;
-  plans.reserve(n);
-  for (size_t i = 0; i < n; ++i) {
-    const auto& q = geom[i];
-    TORCH_CHECK(q.size() == 15, "conv_mfma_fwd_grouped: geom needs 15 ints");
-    TORCH_CHECK(xs[i].device() == xs[0].device());
-    plans.push_back(plan_conv(xs[i], ws_packed[i], q[0], q[1], q[2], q[3],
-                              q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11],
-                              q[12], q[13], scales[i], shifts[i], residuals[i],
-                              acts[i] != 0, residual_posts[i],
-                              residual_post2s[i], q[14]));
-  }
-  auto stream = at::hip::getCurrentHIPStream().stream();
-  const auto f32 = xs[0].options().dtype(torch::kFloat32);
-  std::vector<Tensor> keep;
-  for (size_t first = 0; first < n; first += ibp::kMaxGroup) {
-    const size_t last = std::min(n, first + (size_t)ibp::kMaxGroup);
-    if (last - first == 1) {
-      ConvPlan& plan = plans[first];
-      if (plan.ws_elems > 0) {
-        keep.push_back(torch::empty({plan.ws_elems}, f32));
-        set_workspace(plan, keep.back().data_ptr<float>());
-      }
-      launch_single(plan, stream);
-    } else {
-      launch_group(plans, first, last, f32, stream, keep);
-    }
-  }
-  std::vector<Tensor> ys;
-  ys.reserve(n);
-  for (auto& plan : plans) ys.push_back(plan.y);
-  return ys;
-}
-
-// {BM, BN, splitk, deep} that a conv with these GEMM extents is planned with
-// (M = N*Ho*Wo, K = KH*KW*Cin) — lets tests assert which tile and split a
-// shape lands on.
-std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K) {
-  const TilePlan t = plan_tile(M, (int)Cout, (int)K);
-  return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
-}
-
-// ---- nearest-x2 upsample folded into a 3x3 conv ----------------------------
 void pack_upfold_weight(const Tensor& w, Tensor& out) {
   TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.dim() == 4 &&
               w.scalar_type() == at::ScalarType::BFloat16 &&
@@ -1357,75 +891,242 @@ void pack_upfold_weight(const Tensor& w, Tensor& out) {
 
 namespace {
 
-// The four parities are one logical conv: tile from M = 4*M_low rows, split
-// from all 4*ntiles tiles, the same choice for every parity. (Planned one by
-// one, the 128^2 refine conv would take BM=64 and split 2 although its 1024
-// tiles already fill the chip.) Tiles do not straddle parities, so n_mtiles
-// and ntiles are per parity.
-TilePlan plan_upfold_tile(long long M_low, int Cout, int Cin) {
-  TilePlan t;
-  pick_tile(4 * M_low, Cout, t.BM, t.BN);
-  t.n_mtiles = (int)((M_low + t.BM - 1) / t.BM);
-  t.ntiles = t.n_mtiles * ((Cout + t.BN - 1) / t.BN);
-  const int nk_total = (4 * Cin + ibp::BK - 1) / ibp::BK;
-  t.splitk = pick_split(4 * t.ntiles, nk_total);
-  t.nk_block = (nk_total + t.splitk - 1) / t.splitk;
-  t.deep = t.nk_block <= 6;
-  return t;
+using ibp::ConvPlan;
+using ibp::ConvProblem;
+
+const unsigned short* bf16_ptr(const OptTensor& t) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::ScalarType::BFloat16,
+              "conv_mfma: residuals must be bf16 device tensors");
+  return reinterpret_cast<const unsigned short*>(t->data_ptr());
+}
+
+// One conv as the planner sees it, all but the output pointer: geom = {N, H,
+// W, Cin, Cout, KH, KW, stride, pad_h, pad_w, dil_h, dil_w, Ho, Wo, zs}.
+ConvProblem make_problem(const Tensor& x, const Tensor& w_packed,
+                         const std::vector<int64_t>& geom,
+                         const OptTensor& scale, const OptTensor& shift,
+                         const OptTensor& residual, bool act,
+                         const OptTensor& residual_post,
+                         const OptTensor& residual_post2) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::ScalarType::BFloat16,
+              "conv_mfma: x must be a bf16 device tensor");
+  TORCH_CHECK(w_packed.is_contiguous(), "conv_mfma: pack must be contiguous");
+  TORCH_CHECK(geom.size() == 15, "conv_mfma: geom needs 15 ints");
+  ConvProblem q;
+  ibp::ConvParams& p = q.p;
+  int* const row[15] = {&p.N, &p.H, &p.W, &p.Cin, &p.Cout, &p.KH, &p.KW,
+                        &p.stride, &p.pad_h, &p.pad_w, &p.dil_h, &p.dil_w,
+                        &p.Ho, &p.Wo, &p.zs};
+  for (int i = 0; i < 15; ++i) *row[i] = (int)geom[i];
+  p.x = reinterpret_cast<const unsigned short*>(x.data_ptr());
+  p.w = reinterpret_cast<const unsigned short*>(w_packed.data_ptr());
+  p.scale = scale.has_value() ? scale->data_ptr<float>() : nullptr;
+  p.shift = shift.has_value() ? shift->data_ptr<float>() : nullptr;
+  p.res = bf16_ptr(residual);
+  p.res_post = bf16_ptr(residual_post);
+  p.res_post2 = bf16_ptr(residual_post2);
+  p.act = act ? 1 : 0;
+  return q;
+}
+
+Tensor alloc_output(ConvProblem& q, const Tensor& x) {
+  Tensor y = torch::empty({q.p.N, q.p.Ho, q.p.Wo, q.p.Cout}, x.options());
+  q.p.y = reinterpret_cast<unsigned short*>(y.data_ptr());
+  return y;
+}
+
+// a runtime flag as a template argument: f(std::true_type{} / false_type{})
+template <class F>
+void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// f(BM, BN, DEEP) with the plan's tile as integral constants
+template <class F>
+void with_tile(const ConvPlan& plan, F&& f) {
+  using i128 = std::integral_constant<int, 128>;
+  using i64 = std::integral_constant<int, 64>;
+  using i32 = std::integral_constant<int, 32>;
+  with_flag(plan.t.deep, [&](auto deep) {
+    if (plan.t.BM == 128 && plan.t.BN == 128) f(i128{}, i128{}, deep);
+    else if (plan.t.BM == 128) f(i128{}, i64{}, deep);
+    else if (plan.t.BM == 64) f(i64{}, i64{}, deep);
+    else f(i32{}, i64{}, deep);
+  });
+}
+
+void launch_single(const ConvPlan& plan, hipStream_t stream) {
+  const ibp::ConvParams& p = plan.p;
+  TORCH_CHECK(!p.up, "upfold plans launch through the grouped kernel");
+  with_tile(plan, [&](auto bm, auto bn, auto deep) {
+    hipLaunchKernelGGL(
+        (ibp::conv_mfma_kernel<decltype(bm)::value, decltype(bn)::value,
+                               decltype(deep)::value>),
+        dim3(plan.nblocks), dim3(256), 0, stream, p);
+  });
+  if (p.splitk > 1)
+    with_flag(plan.vec_combine, [&](auto vec) {
+      hipLaunchKernelGGL(ibp::splitk_combine_kernel<decltype(vec)::value>,
+                         dim3(ibp::combine_blocks(plan)), dim3(256), 0, stream,
+                         p.ws, p.y, p.scale, p.shift, p.res, p.res_post,
+                         p.res_post2, (long long)p.M * p.Cout, p.Cout, p.act,
+                         p.splitk);
+    });
+}
+
+void launch_group(const ibp::GroupPlan& gp, hipStream_t stream) {
+  with_flag(gp.up, [&](auto up) {
+    hipLaunchKernelGGL(ibp::conv_mfma_grouped_kernel<decltype(up)::value>,
+                       dim3(gp.blocks), dim3(256), 0, stream, gp.g);
+    if (gp.cg.n > 0)
+      hipLaunchKernelGGL(
+          ibp::splitk_combine_grouped_kernel<decltype(up)::value>,
+          dim3(gp.cblocks), dim3(256), 0, stream, gp.cg);
+  });
+}
+
+// Launch the plans in list order, at most kMaxGroup per launch: a chunk of one
+// plain conv through its own kernel, with exactly its own workspace; every
+// other chunk grouped, one shared workspace. Workspaces outlive the launches.
+void run_plans(std::vector<ConvPlan>& plans, hipStream_t stream,
+               const at::TensorOptions& f32) {
+  std::vector<Tensor> keep;
+  auto workspace = [&](long long elems) -> float* {
+    if (elems <= 0) return nullptr;
+    keep.push_back(torch::empty({elems}, f32));
+    return keep.back().data_ptr<float>();
+  };
+  for (size_t first = 0; first < plans.size(); first += ibp::kMaxGroup) {
+    const size_t last =
+        std::min(plans.size(), first + (size_t)ibp::kMaxGroup);
+    ConvPlan& head = plans[first];
+    if (last - first == 1 && !head.p.up) {
+      if (head.ws_elems > 0) ibp::set_workspace(head, workspace(head.ws_elems));
+      launch_single(head, stream);
+    } else {
+      float* ws = workspace(ibp::group_workspace(plans, first, last));
+      launch_group(ibp::assemble_group(plans, first, last, ws), stream);
+    }
+  }
 }
 
 }  // namespace
+
+Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed,
+                     const std::vector<int64_t>& geom, const OptTensor& scale,
+                     const OptTensor& shift, const OptTensor& residual,
+                     bool act, const OptTensor& residual_post,
+                     const OptTensor& residual_post2) {
+  ConvProblem q = make_problem(x, w_packed, geom, scale, shift, residual, act,
+                               residual_post, residual_post2);
+  Tensor y = alloc_output(q, x);
+  std::vector<ConvPlan> plans{ibp::plan_conv(q)};
+  run_plans(plans, at::hip::getCurrentHIPStream().stream(),
+            x.options().dtype(torch::kFloat32));
+  return y;
+}
+
+// Several independent convs in as few launches as possible: lists of the
+// conv_mfma_fwd arguments, outputs in list order. Every member keeps the plan
+// it gets alone — same tile, split, epilogue path and summation order — so
+// each output is bit-identical to the single call.
+std::vector<Tensor> conv_mfma_fwd_grouped(
+    const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
+    const std::vector<std::vector<int64_t>>& geom,
+    const std::vector<OptTensor>& scales, const std::vector<OptTensor>& shifts,
+    const std::vector<OptTensor>& residuals, const std::vector<bool>& acts,
+    const std::vector<OptTensor>& residual_posts,
+    const std::vector<OptTensor>& residual_post2s) {
+  const size_t n = xs.size();
+  TORCH_CHECK(n > 0 && ws_packed.size() == n && geom.size() == n &&
+              scales.size() == n && shifts.size() == n &&
+              residuals.size() == n && acts.size() == n &&
+              residual_posts.size() == n && residual_post2s.size() == n,
+              "conv_mfma_fwd_grouped: argument lists differ in length");
+  std::vector<ConvPlan> plans;
+  std::vector<Tensor> ys;
+  plans.reserve(n);
+  ys.reserve(n);
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(xs[i].device() == xs[0].device());
+    ConvProblem q = make_problem(xs[i], ws_packed[i], geom[i], scales[i],
+                                 shifts[i], residuals[i], acts[i],
+                                 residual_posts[i], residual_post2s[i]);
+    ys.push_back(alloc_output(q, xs[i]));
+    plans.push_back(ibp::plan_conv(q));
+  }
+  run_plans(plans, at::hip::getCurrentHIPStream().stream(),
+            xs[0].options().dtype(torch::kFloat32));
+  return ys;
+}
 
 // y[N, 2H, 2W, Cout] = epilogue(conv3x3(nearest_x2(x_low), W, pad 1)) as
 // four stride-1 2x2 convs over x_low [N, H, W, Cin], one per output parity
 // (py, px), with pad (1-py, 1-px) and the folded weights of
 // pack_upfold_weight; each stores into its own pixels of the shared output.
-// One grouped conv launch, at most one grouped combine.
+// geom is the layer's row: 3x3 over H x W = the LOW resolution, Ho x Wo =
+// 2H x 2W. One grouped conv launch, at most one grouped combine.
 Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
-                            int64_t N, int64_t H, int64_t W, int64_t Cin,
-                            int64_t Cout, const c10::optional<Tensor>& scale,
-                            const c10::optional<Tensor>& shift, bool act,
-                            const c10::optional<Tensor>& residual_post,
-                            const c10::optional<Tensor>& residual_post2) {
-  TORCH_CHECK(x_low.is_cuda() && x_low.is_contiguous() &&
-              x_low.numel() == N * H * W * Cin,
+                            const std::vector<int64_t>& geom,
+                            const OptTensor& scale, const OptTensor& shift,
+                            bool act, const OptTensor& residual_post,
+                            const OptTensor& residual_post2) {
+  ConvProblem q = make_problem(x_low, packs, geom, scale, shift, c10::nullopt,
+                               act, residual_post, residual_post2);
+  ibp::ConvParams& p = q.p;
+  const int64_t N = p.N, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout;
+  TORCH_CHECK(p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad_h == 1 &&
+              p.pad_w == 1 && p.dil_h == 1 && p.dil_w == 1 && p.zs == 1 &&
+              p.Ho == 2 * H && p.Wo == 2 * W,
+              "conv_mfma_upfold_fwd: geom must be a 3x3 stride-1 pad-1 conv "
+              "with Ho x Wo = 2H x 2W");
+  TORCH_CHECK(x_low.is_contiguous() && x_low.numel() == N * H * W * Cin,
               "conv_mfma_upfold_fwd: x_low must be contiguous [N][H][W][Cin]");
-  TORCH_CHECK(packs.is_cuda() && packs.is_contiguous() &&
+  TORCH_CHECK(packs.is_cuda() &&
               packs.scalar_type() == at::ScalarType::BFloat16 &&
               packs.numel() == 16 * Cout * Cin,
               "conv_mfma_upfold_fwd: packs must be bf16 [4][Cout][4*Cin]");
   for (const auto* r : {&residual_post, &residual_post2})
-    TORCH_CHECK(!r->has_value() ||
-                ((*r)->is_cuda() &&
-                 (*r)->scalar_type() == at::ScalarType::BFloat16 &&
-                 (*r)->numel() == 4 * N * H * W * Cout),
+    TORCH_CHECK(!r->has_value() || (*r)->numel() == 4 * N * H * W * Cout,
                 "conv_mfma_upfold_fwd: residuals must be bf16 "
                 "[N][2H][2W][Cout]");
-  UpFold up;
-  up.y = torch::empty({N, 2 * H, 2 * W, Cout}, x_low.options());
-  up.t = plan_upfold_tile((long long)N * H * W, (int)Cout, (int)Cin);
+  Tensor y = alloc_output(q, x_low);
+  // each parity: a 2x2 conv whose rows index the low-resolution grid
+  p.KH = p.KW = 2;
+  p.Ho = p.H;
+  p.Wo = p.W;
+  p.up = 1;
+  q.tile = ibp::plan_upfold_tile(N * H * W, p.Cout, p.Cin);
   std::vector<ConvPlan> plans;
   plans.reserve(4);
   for (int par = 0; par < 4; ++par) {
-    up.py = par >> 1;
-    up.px = par & 1;
-    up.w = reinterpret_cast<const unsigned short*>(packs.data_ptr()) +
-           (long long)par * Cout * 4 * Cin;
-    plans.push_back(plan_conv(x_low, packs, N, H, W, Cin, Cout, 2, 2, 1,
-                              1 - up.py, 1 - up.px, 1, 1, H, W, scale, shift,
-                              c10::nullopt, act, residual_post,
-                              residual_post2, 1, &up));
+    p.py = par >> 1;
+    p.px = par & 1;
+    p.pad_h = 1 - p.py;
+    p.pad_w = 1 - p.px;
+    p.w = reinterpret_cast<const unsigned short*>(packs.data_ptr()) +
+          (long long)par * Cout * 4 * Cin;
+    plans.push_back(ibp::plan_conv(q));
   }
-  std::vector<Tensor> keep;
-  launch_group(plans, 0, 4, x_low.options().dtype(torch::kFloat32),
-               at::hip::getCurrentHIPStream().stream(), keep);
-  return up.y;
+  run_plans(plans, at::hip::getCurrentHIPStream().stream(),
+            x_low.options().dtype(torch::kFloat32));
+  return y;
+}
+
+// {BM, BN, splitk, deep} that a conv with these GEMM extents is planned with
+// (M = N*Ho*Wo, K = KH*KW*Cin) — lets tests assert which tile and split a
+// shape lands on.
+std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K) {
+  const ibp::TilePlan t = ibp::plan_tile(M, (int)Cout, (int)K);
+  return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
 }
 
 // {BM, BN, splitk, deep} shared by the four parities of an upfold conv over
 // M_low = N*H*W low-resolution pixels.
 std::vector<int64_t> conv_mfma_upfold_plan(int64_t M_low, int64_t Cout,
                                            int64_t Cin) {
-  const TilePlan t = plan_upfold_tile(M_low, (int)Cout, (int)Cin);
+  const ibp::TilePlan t = ibp::plan_upfold_tile(M_low, (int)Cout, (int)Cin);
   return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
 }

@@ -18,6 +18,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+# the member lists and the plans they must land on: shared with the CPU
+# planner test
+from conv_plan_cases import (EXACT_PLANS, EXACT_SPECS, G1, G1_BM, G3, G3_BM,
+                             GL, GL_TILE_DEEP, GROUPS, TILE_CONFIGS)
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -63,35 +68,6 @@ def _member(gen, size, cin, cout, k, epi):
     return m
 
 
-FULL = ("scale", "act", "res", "post", "post2")
-
-# (size, cin, cout, k, epilogue)
-G3 = [(96, 64, 64, 3, FULL), (48, 128, 128, 3, ()),
-      (24, 192, 50, 3, ("scale", "act")), (12, 64, 72, 3, ("scale", "post")),
-      (6, 128, 64, 3, FULL)]
-# 1x1 (DEEP); Cin = 64 is a single K-chunk: unsplit members beside split
-# ones, on the 16-byte-store lane exchange (Cout 64 and 72) and the pair path
-G1 = [(96, 64, 64, 1, FULL), (48, 128, 128, 1, ("scale", "post")),
-      (24, 64, 72, 1, ("scale", "act")), (12, 192, 50, 1, FULL),
-      (6, 64, 50, 1, ())]
-# long K (Cin 192/384) and wide Cout: few enough splits that a block keeps
-# more than 6 K-chunks, i.e. the non-DEEP bodies of all four tiles, plus the
-# 128x128 and 128x64 DEEP ones
-GL = [(96, 192, 256, 3, FULL), (96, 192, 192, 3, ("scale", "act")),
-      (48, 192, 256, 3, ()), (24, 384, 256, 3, ("scale", "post")),
-      (6, 384, 64, 3, FULL), (96, 128, 256, 1, ("scale", "post2")),
-      (96, 128, 192, 1, FULL)]
-GROUPS = {
-    "3x3-mixed": G3,
-    "1x1-mixed": G1,
-    "long-k-non-deep": GL,
-    "group-of-1": G3[:1],
-    "group-of-2-unsplit": [G1[0], G1[2]],
-    "group-of-8": G3 + G1[:3],
-    "list-of-9": G1 + G3[:4],
-}
-
-
 def _plan(size, cin, cout, k, _epi=None):
     """(BM, BN, splitk, deep) the host plans for a member (N = 1)."""
     ext = _backend.hip_extension()
@@ -101,25 +77,20 @@ def _plan(size, cin, cout, k, _epi=None):
 def test_member_shapes_land_on_the_plans_the_groups_are_meant_to_mix():
     """The groups above only test what their names say while the planner
     keeps putting their members on these tiles and splits."""
-    assert [_plan(*m)[0] for m in G3] == [128, 64, 32, 32, 32]
-    assert [_plan(*m)[0] for m in G1] == [128, 64, 32, 32, 32]
+    assert [_plan(*m)[0] for m in G3] == G3_BM == [128, 64, 32, 32, 32]
+    assert [_plan(*m)[0] for m in G1] == G1_BM == [128, 64, 32, 32, 32]
     assert all(_plan(*m)[2] > 1 for m in G3)
     # 1x1 with Cin = 64 is a single K-chunk: unsplit beside split members
     assert [_plan(*m)[2] == 1 for m in G1] == [m[1] == 64 for m in G1]
     assert all(_plan(*m)[3] == 1 for m in G1)
-    assert [_plan(*m)[:2] + _plan(*m)[3:] for m in GL] == [
-        (128, 128, 0), (128, 64, 0), (64, 64, 0), (32, 64, 0), (32, 64, 1),
-        (128, 128, 1), (128, 64, 1)]
+    assert [_plan(*m)[:2] + _plan(*m)[3:] for m in GL] == GL_TILE_DEEP
     # every tile configuration of the grouped kernel's switch is exercised
     seen = {_plan(*m)[:2] + _plan(*m)[3:] for m in G3 + G1 + GL}
-    assert seen == {(bm, bn, d) for bm, bn in
-                    [(128, 128), (128, 64), (64, 64), (32, 64)]
-                    for d in (0, 1)}
+    assert seen == TILE_CONFIGS and len(TILE_CONFIGS) == 8
     # the exact-integer group: one unsplit non-DEEP member, split and
     # unsplit DEEP ones
-    assert [_plan(s, ci, co, k) for s, ci, co, k, _ in EXACT_SPECS] == [
-        (128, 64, 1, 0), (64, 64, 1, 1), (32, 64, 9, 1), (32, 64, 1, 1),
-        (32, 64, 9, 1)]
+    assert [_plan(s, ci, co, k) for s, ci, co, k, _ in EXACT_SPECS] \
+        == EXACT_PLANS
 
 
 @pytest.mark.parametrize("name", list(GROUPS))
@@ -154,13 +125,6 @@ def test_group_outputs_do_not_depend_on_list_order():
     rev = conv_kernels.conv_fwd_group(members[::-1])[::-1]
     for a, b in zip(fwd, rev):
         assert torch.equal(a, b)
-
-
-# (size, cin, cout, k, full epilogue); 226^2 = 399 * 128 + 4 rows fills the
-# chip without split-K: 9 K-chunks per block, the non-DEEP body
-EXACT_SPECS = [(226, 64, 64, 3, True), (48, 64, 128, 1, False),
-               (24, 64, 50, 3, True), (12, 64, 72, 1, True),
-               (6, 64, 64, 3, False)]
 
 
 def _draw(gen, shape, values, probs):

@@ -20,6 +20,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+# the integer cases and the plans they must land on: shared with the CPU
+# planner test
+from conv_plan_cases import (INT_CASES, UPFOLD_CASE_PLANS,
+                             UPFOLD_CASE_PLANS_TARGET_1, UPFOLD_SHAPE_PLANS,
+                             UPFOLD_SPLITS_BELOW_12)
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -89,63 +95,32 @@ def test_pack_equals_host_fold_bit_for_bit(cout, cin):
 # plans
 # ---------------------------------------------------------------------------
 
-# (name, N, Cin, Cout, low H, low W, residual offset in bytes, IBP_SPLITK_TARGET,
-#  full epilogue)
-INT_CASES = [
-    # odd sizes, borders dominate, M_low < one tile; split 4 over 4 K-chunks:
-    # 16-byte slab stores past a half-empty column tile, vector combine
-    ("5x7-split", 1, 64, 40, 5, 7, 0, None, True),
-    # the same problem unsplit (the planner's documented override): the
-    # vec_epi = 2 lane exchange with a half-empty 16-byte store pair
-    ("5x7-unsplit", 1, 64, 40, 5, 7, 0, "1", True),
-    # 32-row tile, split-K with scatter in slabs and vector combine
-    ("8x8-split", 2, 64, 64, 8, 8, 0, None, True),
-    # non-square, 64-row tile, Cout tail, split, vector combine
-    ("16x24-cout72", 2, 128, 72, 16, 24, 0, None, True),
-    # 128x128 tile, unsplit vec_epi = 2 lane exchange with scatter; N = 12
-    # is the smallest batch at which 4 x 96 tiles fill the chip unsplit
-    ("32x32-unsplit", 12, 64, 128, 32, 32, 0, None, True),
-    # residuals 8-byte but not 16-byte aligned: the scalar combine body
-    ("8x8-res-off8", 2, 64, 64, 8, 8, 8, None, True),
-    # no activation, no residuals, no scale/shift
-    ("8x8-plain", 2, 64, 64, 8, 8, 0, None, False),
-    # Cout % 8 != 0 (outside the model's gate, inside the op's): the 8-byte
-    # vec_epi = 1 stores, the 4-byte pair stores and the per-element path,
-    # split (slab stores of each width, scalar combine) and unsplit
-    ("5x7-cout36-split", 1, 64, 36, 5, 7, 0, None, True),
-    ("5x7-cout36-unsplit", 1, 64, 36, 5, 7, 0, "1", True),
-    ("5x7-cout34-split", 1, 64, 34, 5, 7, 0, None, True),
-    ("5x7-cout34-unsplit", 1, 64, 34, 5, 7, 0, "1", True),
-    ("5x7-cout33-unsplit", 1, 64, 33, 5, 7, 0, "1", True),
-]
-
-
 def test_cases_hit_the_paths_they_are_named_for(monkeypatch):
     monkeypatch.delenv("IBP_SPLITK_TARGET", raising=False)
     monkeypatch.delenv("IBP_CONV_BM", raising=False)
     # the workload's four refine convs, batch 4: one plan for all parities,
     # from M = 4 * M_low rows and 4 * ntiles tiles
-    assert _plan(4, 256, 256, 64, 64) == (128, 128, 1, 0)
-    assert _plan(4, 384, 384, 32, 32) == (128, 128, 1, 0)
-    assert _plan(4, 512, 512, 16, 16) == (64, 64, 1, 0)
-    assert _plan(4, 640, 640, 8, 8) == (32, 64, 2, 0)
+    # ... and the precision shape: 2 x 256 -> 256 at 16 x 16, non-DEEP split
+    assert len(UPFOLD_SHAPE_PLANS) == 5
+    for shape, want in UPFOLD_SHAPE_PLANS:
+        assert _plan(*shape) == want, shape
     by_name = {c[0]: c for c in INT_CASES}
 
     def plan_of(name):
         _, n, cin, cout, h, w, *_ = by_name[name]
         return _plan(n, cin, cout, h, w)
 
-    assert plan_of("5x7-split") == (32, 64, 4, 1)
-    assert plan_of("8x8-split") == (32, 64, 4, 1)
-    assert plan_of("16x24-cout72") == (64, 64, 4, 1)
-    assert plan_of("32x32-unsplit") == (128, 128, 1, 1)
-    assert _plan(11, 64, 128, 32, 32)[2] > 1      # one image fewer splits
-    assert plan_of("8x8-res-off8") == (32, 64, 4, 1)
-    # the precision shape: 2 x 256 -> 256 at 16 x 16, non-DEEP split
-    assert _plan(2, 256, 256, 16, 16) == (32, 64, 2, 0)
+    assert set(UPFOLD_CASE_PLANS) == {
+        "5x7-split", "8x8-split", "16x24-cout72", "32x32-unsplit",
+        "8x8-res-off8"}
+    for name, want in UPFOLD_CASE_PLANS.items():
+        assert plan_of(name) == want, name
+    assert _plan(*UPFOLD_SPLITS_BELOW_12)[2] > 1  # one image fewer splits
     monkeypatch.setenv("IBP_SPLITK_TARGET", "1")
-    assert plan_of("5x7-unsplit") == (32, 64, 1, 1)
-    assert plan_of("5x7-cout33-unsplit") == (32, 64, 1, 1)
+    assert set(UPFOLD_CASE_PLANS_TARGET_1) == {"5x7-unsplit",
+                                               "5x7-cout33-unsplit"}
+    for name, want in UPFOLD_CASE_PLANS_TARGET_1.items():
+        assert plan_of(name) == want, name
 
 
 # ---------------------------------------------------------------------------
