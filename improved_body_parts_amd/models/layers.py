@@ -140,13 +140,14 @@ class Residual(nn.Module):
         cb = self.convBlock
         y = ops.conv_bn_act(x, cb[0], cb[1], act=True, training=self.training)
         y = ops.conv_bn_act(y, cb[3], cb[4], act=True, training=self.training)
-        # last conv+bn fuses the residual add (+ optional relu) on the HIP path
+        # last conv+bn fuses the residual add (+ optional relu) on the HIP path;
+        # a projection shortcut is a second input of that conv where the op
+        # allows it (bf16 inference), else a conv of its own
         if self.ins != self.outs:
-            residual = ops.conv_bn_act(x, self.skipConv[0], self.skipConv[1], act=False,
-                                       training=self.training)
-        else:
-            residual = x
-        return ops.conv_bn_add_act(y, cb[6], cb[7], residual, act=self.relu_flag,
+            return ops.conv_bn_add_conv_bn_act(
+                y, cb[6], cb[7], x, self.skipConv[0], self.skipConv[1],
+                act=self.relu_flag, training=self.training)
+        return ops.conv_bn_add_act(y, cb[6], cb[7], x, act=self.relu_flag,
                                    training=self.training)
 
 

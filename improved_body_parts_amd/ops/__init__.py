@@ -97,6 +97,23 @@ def conv_bn_add_act(x, conv, bn, residual, act: bool, training: bool,
     return y
 
 
+def conv_bn_add_conv_bn_act(y, conv_a, bn_a, x, conv_b, bn_b, act: bool,
+                            training: bool):
+    """``conv_bn_add_act(y, conv_a, bn_a, conv_bn_act(x, conv_b, bn_b,
+    act=False), act)`` — a Residual block's last conv with its projection
+    shortcut. On the HIP bf16 inference path two plain 1x1 convs run as one
+    conv over K = Ca + Cb that reads both inputs, and the shortcut's output
+    is never written (see ``conv.conv_bn_add_conv_bn_act_hip``; switch off
+    with ``IBP_SKIP_FOLD=0``). Elsewhere it is the two calls."""
+    if use_hip_for(y):
+        from . import conv as _conv
+        return _conv.conv_bn_add_conv_bn_act_hip(
+            y, conv_a, bn_a, x, conv_b, bn_b, act=act, training=training)
+    residual = conv_bn_act(x, conv_b, bn_b, act=False, training=training)
+    return conv_bn_add_act(y, conv_a, bn_a, residual, act=act,
+                           training=training)
+
+
 def conv_bn_act_group(items):
     """Several INDEPENDENT :func:`conv_bn_act` / :func:`conv_bn_add_act`
     calls — ``items`` is a list of dicts with keys ``x conv bn act`` and

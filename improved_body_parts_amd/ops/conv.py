@@ -311,6 +311,79 @@ def upsample_conv_bn_act_hip(low, conv, bn, act: bool, training: bool = False,
                            residual_post2=residual_post2)
 
 
+def skip_fold_enabled() -> bool:
+    """``IBP_SKIP_FOLD=0`` (read at call time) restores the projection
+    shortcut as a conv of its own for A/B runs."""
+    return os.environ.get("IBP_SKIP_FOLD", "1") != "0"
+
+
+def _branch_fold(conv, bn):
+    """(scale, shift) of one branch, computed afresh: eval-mode BN fold, else
+    (None, bias), else (None, None)."""
+    if bn is not None and bn.weight is not None:
+        return _fold_bn(None, bn)
+    return None, (conv.bias.detach().float() if conv.bias is not None else None)
+
+
+def _fold_versions(conv, bn):
+    if bn is not None and bn.weight is not None:
+        return (conv.weight._version, bn.weight._version, bn.bias._version,
+                bn.running_mean._version, bn.running_var._version)
+    bias = conv.bias
+    return (conv.weight._version, bias._version if bias is not None else -1)
+
+
+def cat_fold(conv_a, bn_a, conv_b, bn_b):
+    """``(pack, ones, shift)`` of the two-source conv that computes
+    ``bn_a(conv_a(.)) + bn_b(conv_b(.))`` in eval mode: both folded scales
+    ride the weight rows, the shifts add up. One pack launch per version of
+    anything that enters either fold — both weights, each BN's weight, bias,
+    running mean and running var, or the conv bias without BN. Cached on the
+    first conv's weight, one entry per partner."""
+    wb = conv_b.weight
+    return versioned(conv_a.weight, ("cat", id(wb), id(bn_a), id(bn_b)),
+                     _fold_versions(conv_a, bn_a) + _fold_versions(conv_b, bn_b),
+                     _cat_build, conv_a, bn_a, conv_b, bn_b)[0]
+
+
+def _cat_build(prev, conv_a, bn_a, conv_b, bn_b):
+    scale_a, shift_a = _branch_fold(conv_a, bn_a)
+    scale_b, shift_b = _branch_fold(conv_b, bn_b)
+    packed = conv_kernels.cat_pack(prev[0] if prev is not None else None,
+                                   conv_a.weight, conv_b.weight, scale_a,
+                                   scale_b, shift_a, shift_b)
+    # the partners stay alive with the entry, so their ids (in the tag)
+    # cannot be handed to other objects
+    return packed, (conv_b.weight, bn_a, bn_b)
+
+
+def _plain_1x1(conv):
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.padding == (0, 0) and conv.dilation == (1, 1)
+            and conv.groups == 1)
+
+
+def conv_bn_add_conv_bn_act_hip(y, conv_a, bn_a, x, conv_b, bn_b, act: bool,
+                                training: bool = False):
+    """``act(bn_a(conv_a(y)) + bn_b(conv_b(x)))`` — the tail of a Residual
+    block with a projection shortcut. On the bf16 inference path (grad
+    disabled, both BNs in eval mode) two plain 1x1 convs with equal Cout and
+    ``conv_a.in_channels % 64 == 0`` run as ONE conv over both inputs
+    (``conv_kernels.conv_cat_fwd``); everything else runs the two calls:
+    ``conv_b`` on its own, its output the pre-act residual of ``conv_a``."""
+    if skip_fold_enabled() and _on_inference_path(y, bn_a, training) \
+            and _on_inference_path(x, bn_b, training) \
+            and _plain_1x1(conv_a) and _plain_1x1(conv_b) \
+            and conv_kernels.cat_supported(y, conv_a.weight, x, conv_b.weight):
+        pack, ones, shift = cat_fold(conv_a, bn_a, conv_b, bn_b)
+        return conv_kernels.conv_cat_fwd(y, conv_a.weight, x, conv_b.weight,
+                                         pack, scale=ones, shift=shift,
+                                         act=act)
+    residual = conv_bn_act_hip(x, conv_b, bn_b, act=False, training=training)
+    return conv_bn_act_hip(y, conv_a, bn_a, act=act, residual=residual,
+                           training=training)
+
+
 def conv_group_enabled() -> bool:
     """``IBP_CONV_GROUP=0`` (read at call time) restores one launch per conv
     for A/B runs."""

@@ -329,6 +329,92 @@ def upfold_fwd(x_low, weight, scale=None, shift=None, act=False,
     return y.permute(0, 3, 1, 2)
 
 
+# ---------------------------------------------------------------------------
+# two 1x1 convs whose outputs are only added: one conv over both inputs
+# ---------------------------------------------------------------------------
+# act(sa.(Wa.a) + ta + sb.(Wb.b) + tb) = act([sa.Wa | sb.Wb] . [a | b] + (ta + tb))
+# One GEMM over K = Ca + Cb whose A rows come from two tensors (the kernel's
+# CAT gather); the per-channel scales move into the weight rows, which costs
+# one more bf16 rounding of the weights, and the second conv's output is never
+# written (docs/KERNELS.md, "Two-source 1x1 conv").
+
+def cat_weight_reference(wa, wb, scale_a=None, scale_b=None, shift_a=None,
+                         shift_b=None):
+    """``(pack, shift)`` of the two-source conv, pure torch on the weights'
+    device: pack bf16 ``[Cout][Ca + Cb]`` with source a first, every element
+    ``float(w) * scale[co]`` (one fp32 multiply, scale 1 when absent) rounded
+    to bf16 once; shift fp32 ``shift_a + shift_b`` (absent = 0). Bit-equal to
+    ``pack_cat_weight_kernel``."""
+    cout = wa.shape[0]
+    assert wb.shape[0] == cout and tuple(wa.shape[2:]) == (1, 1) \
+        and tuple(wb.shape[2:]) == (1, 1)
+    halves = []
+    for w, s in ((wa, scale_a), (wb, scale_b)):
+        h = w.detach().to(torch.bfloat16).float().reshape(cout, -1)
+        if s is not None:
+            h = h * s.detach().float().reshape(cout, 1)
+        halves.append(h.to(torch.bfloat16))
+    zero = torch.zeros(cout, dtype=torch.float32, device=wa.device)
+    shift = (zero if shift_a is None else shift_a.detach().float()) \
+        + (zero if shift_b is None else shift_b.detach().float())
+    return torch.cat(halves, dim=1).contiguous(), shift
+
+
+def cat_pack(prev, wa, wb, scale_a, scale_b, shift_a, shift_b):
+    """``(pack, ones, shift)`` for :func:`conv_cat_fwd`: one
+    ``pack_cat_weight_kernel`` launch on GPU bf16 weights (into ``prev``'s
+    buffers when given), the host reference elsewhere. ``ones`` is the unit
+    scale the split-K combine needs beside a shift."""
+    cout = wa.shape[0]
+    k = wa.shape[1] + wb.shape[1]
+    wa, wb = wa.detach(), wb.detach()
+    if wa.is_cuda and wa.dtype == torch.bfloat16 and wb.dtype == wa.dtype:
+        if prev is not None:
+            pack, ones, shift = prev
+        else:
+            pack = torch.empty(cout, k, dtype=torch.bfloat16, device=wa.device)
+            ones = torch.ones(cout, dtype=torch.float32, device=wa.device)
+            shift = torch.empty(cout, dtype=torch.float32, device=wa.device)
+        hip_extension().pack_cat_weight(wa.contiguous(), wb.contiguous(),
+                                        scale_a, scale_b, shift_a, shift_b,
+                                        pack, shift)
+        return pack, ones, shift
+    pack, shift = cat_weight_reference(wa, wb, scale_a, scale_b, shift_a,
+                                       shift_b)
+    return pack, torch.ones_like(shift), shift
+
+
+def cat_supported(a, weight_a, b, weight_b) -> bool:
+    """Envelope of :func:`conv_cat_fwd`: bf16 CUDA inputs over the same
+    pixels, 1x1 weights with equal Cout, Ca % 64 == 0 (every K-chunk inside
+    one source). The second source may have any width."""
+    return (not DISABLE and a.is_cuda and b.is_cuda
+            and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16
+            and tuple(weight_a.shape[2:]) == (1, 1)
+            and tuple(weight_b.shape[2:]) == (1, 1)
+            and weight_a.shape[0] == weight_b.shape[0]
+            and a.shape[1] == weight_a.shape[1]
+            and b.shape[1] == weight_b.shape[1]
+            and weight_a.shape[1] % 64 == 0
+            and a.shape[0] == b.shape[0] and a.shape[2:] == b.shape[2:])
+
+
+def conv_cat_fwd(a, weight_a, b, weight_b, pack, scale=None, shift=None,
+                 act=False, residual_post=None, residual_post2=None):
+    """``act(scale * (pack . [a | b]) + shift) (+ residual_post [+2])`` — the
+    1x1 convs ``weight_a`` over ``a`` and ``weight_b`` over ``b`` as ONE conv
+    over K = Ca + Cb with ``pack`` from :func:`cat_pack` (the weights are
+    passed for their shapes only)."""
+    a = a.contiguous(memory_format=_CL)
+    n, ca, h, w_ = a.shape
+    cout = weight_a.shape[0]
+    geom = [n, h, w_, ca, cout, 1, 1, 1, 0, 0, 1, 1, h, w_, 1]
+    y = hip_extension().conv_mfma_fwd(
+        a, pack, geom, scale, shift, None, bool(act), _cl(residual_post),
+        _cl(residual_post2), b.contiguous(memory_format=_CL))
+    return y.permute(0, 3, 1, 2)
+
+
 def conv_dgrad(dy, weight, x_shape, stride, padding, dilation):
     """dx = stride-1 conv of the (virtually) zero-dilated dy with 180-rotated
     transposed weights; pad' = dil*(K-1) - pad, gather stride zs = stride."""

@@ -65,7 +65,8 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed,
                      const c10::optional<Tensor>& shift,
                      const c10::optional<Tensor>& residual, bool act,
                      const c10::optional<Tensor>& residual_post,
-                     const c10::optional<Tensor>& residual_post2);
+                     const c10::optional<Tensor>& residual_post2,
+                     const c10::optional<Tensor>& x2);
 
 std::vector<Tensor> conv_mfma_fwd_grouped(
     const std::vector<Tensor>& xs, const std::vector<Tensor>& ws_packed,
@@ -83,6 +84,12 @@ void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
                       const c10::optional<Tensor>& dgrad_pack);
 
 void pack_upfold_weight(const Tensor& w, Tensor& out);
+void pack_cat_weight(const Tensor& wa, const Tensor& wb,
+                     const c10::optional<Tensor>& scale_a,
+                     const c10::optional<Tensor>& scale_b,
+                     const c10::optional<Tensor>& shift_a,
+                     const c10::optional<Tensor>& shift_b, Tensor& out,
+                     Tensor& shift_out);
 Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
                             const std::vector<int64_t>& geom,
                             const c10::optional<Tensor>& scale,
@@ -163,7 +170,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = c10::nullopt, py::arg("shift") = c10::nullopt,
         py::arg("residual") = c10::nullopt, py::arg("act") = false,
         py::arg("residual_post") = c10::nullopt,
-        py::arg("residual_post2") = c10::nullopt);
+        py::arg("residual_post2") = c10::nullopt,
+        py::arg("x2") = c10::nullopt);
   m.def("conv_mfma_fwd_grouped", &conv_mfma_fwd_grouped,
         "independent MFMA convs in one grouped launch per 8 (+ one combine)",
         py::arg("xs"), py::arg("ws_packed"), py::arg("geom"),
@@ -180,6 +188,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "3x3 weight -> four folded 2x2 packs [4][Cout][4*Cin] (nearest-x2 "
         "upsample folded into the conv)",
         py::arg("w"), py::arg("out"));
+  m.def("pack_cat_weight", &pack_cat_weight,
+        "two 1x1 weights (+ per-channel scales, shifts) -> one [Cout][Ca+Cb] "
+        "pack and the fused shift of a two-source 1x1 conv",
+        py::arg("wa"), py::arg("wb"), py::arg("scale_a"), py::arg("scale_b"),
+        py::arg("shift_a"), py::arg("shift_b"), py::arg("out"),
+        py::arg("shift_out"));
   m.def("conv_mfma_upfold_fwd", &conv_mfma_upfold_fwd,
         "conv3x3(nearest_x2(x_low)) + epilogue as four parity 2x2 convs in "
         "one grouped launch",

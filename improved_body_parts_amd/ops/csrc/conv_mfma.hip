@@ -71,7 +71,10 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 // UP compiles the output scatter of ConvParams::up in; only the grouped
 // upfold kernel instantiates it, every other kernel is the code it was
 // without it.
-template <int BM, int BN, bool DEEP, bool UP, typename Params>
+//
+// CAT compiles the two-source 1x1 gather of ConvParams::x2 in (and the tap
+// walk out); only conv_mfma_kernel<.., true> instantiates it.
+template <int BM, int BN, bool DEEP, bool UP, bool CAT, typename Params>
 __device__ __forceinline__ void conv_mfma_body(const Params& p,
                                                const int bid,
                                                unsigned short* lds_a,
@@ -157,11 +160,15 @@ __device__ __forceinline__ void conv_mfma_body(const Params& p,
   // chunk per thread) and measured 0.63-0.68x of the round-1 kernel — the
   // emulated 32-bit divide beside MFMAs is exactly the anti-lever the guide
   // warns about.
+  // (CAT: a 1x1 conv over two sources has no taps; k alone is walked)
   int t_kk = k_begin * BK + a_off;
-  int t_f = t_kk / p.Cin;
-  int t_ci = t_kk - t_f * p.Cin;
-  int t_kh = t_f / p.KW;
-  int t_kw = t_f - t_kh * p.KW;
+  int t_ci = 0, t_kh = 0, t_kw = 0;
+  if constexpr (!CAT) {
+    const int t_f = t_kk / p.Cin;
+    t_ci = t_kk - t_f * p.Cin;
+    t_kh = t_f / p.KW;
+    t_kw = t_f - t_kh * p.KW;
+  }
   auto tap_advance = [&](int& ci, int& kh, int& kw, int step) {
     ci += step;
     while (ci >= p.Cin) {
@@ -175,6 +182,29 @@ __device__ __forceinline__ void conv_mfma_body(const Params& p,
   auto load_chunk = [&](int ck, unsigned short (&a_reg)[A_ELEMS],
                         unsigned short (&b_reg)[B_ELEMS]) {
     int kk = t_kk, ci = t_ci, kh = t_kh, kw = t_kw;
+    if constexpr (CAT) {
+      // two sources, one row index: the chunk lies in x (k < Cin) or in x2 —
+      // Cin % BK == 0, so the choice is uniform over the block. x2's width
+      // may be anything: pieces past its end are zero (K-tail), rows that
+      // are not 16-byte aligned (the 50-channel pred) load per element.
+      const bool second = t_kk >= p.Cin;
+      const int C = second ? p.Cin2 : p.Cin;
+      const int c0 = second ? t_kk - p.Cin : t_kk;
+      const unsigned short* src =
+          (second ? p.x2 : p.x) + (long long)a_m * C + c0;
+      const bool aligned = ((reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+      if (a_valid_row && aligned && c0 + A_ELEMS <= C) {
+        #pragma unroll
+        for (int v = 0; v < A_ELEMS / 8; ++v)
+          *reinterpret_cast<ushortv8*>(&a_reg[v * 8]) =
+              *reinterpret_cast<const ushortv8*>(src + v * 8);
+      } else {
+        #pragma unroll
+        for (int e = 0; e < A_ELEMS; ++e)
+          a_reg[e] = (a_valid_row && c0 + e < C) ? src[e] : (unsigned short)0;
+      }
+      goto a_done;
+    }
     // fast path: the whole A_ELEMS piece inside one filter tap (all the
     // Cin % 64 == 0 hourglass convs) — ONE predicate set, straight-line
     // vector loads (the per-subpiece form below costs ~10% on hot shapes)
@@ -260,7 +290,7 @@ __device__ __forceinline__ void conv_mfma_body(const Params& p,
 a_done:
     // walk the persistent state one full chunk forward
     t_kk += BK;
-    tap_advance(t_ci, t_kh, t_kw, BK);
+    if constexpr (!CAT) tap_advance(t_ci, t_kh, t_kw, BK);
     // ---- B: packed [Cout][K] rows
     {
       int col = n0 + b_row;
@@ -559,11 +589,11 @@ a_done:
   }
 }
 
-template <int BM, int BN, bool DEEP = false>
+template <int BM, int BN, bool DEEP = false, bool CAT = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
   __shared__ unsigned short lds_a[2 * BM * BK];
   __shared__ unsigned short lds_b[2 * BN * BK];
-  conv_mfma_body<BM, BN, DEEP, false>(p, blockIdx.x, lds_a, lds_b);
+  conv_mfma_body<BM, BN, DEEP, false, CAT>(p, blockIdx.x, lds_a, lds_b);
 }
 
 // ---- grouped launch --------------------------------------------------------
@@ -606,21 +636,21 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
   const int bid = gb - base;
   switch (cfg) {
     case tile_cfg(128, 128, false):
-      conv_mfma_body<128, 128, false, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 128, false, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 128, true):
-      conv_mfma_body<128, 128, true, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 128, true, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 64, false):
-      conv_mfma_body<128, 64, false, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 64, false, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(128, 64, true):
-      conv_mfma_body<128, 64, true, UP>(p, bid, lds, lds + 2 * 128 * BK); break;
+      conv_mfma_body<128, 64, true, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
     case tile_cfg(64, 64, false):
-      conv_mfma_body<64, 64, false, UP>(p, bid, lds, lds + 2 * 64 * BK); break;
+      conv_mfma_body<64, 64, false, UP, false>(p, bid, lds, lds + 2 * 64 * BK); break;
     case tile_cfg(64, 64, true):
-      conv_mfma_body<64, 64, true, UP>(p, bid, lds, lds + 2 * 64 * BK); break;
+      conv_mfma_body<64, 64, true, UP, false>(p, bid, lds, lds + 2 * 64 * BK); break;
     case tile_cfg(32, 64, false):
-      conv_mfma_body<32, 64, false, UP>(p, bid, lds, lds + 2 * 32 * BK); break;
+      conv_mfma_body<32, 64, false, UP, false>(p, bid, lds, lds + 2 * 32 * BK); break;
     default:
-      conv_mfma_body<32, 64, true, UP>(p, bid, lds, lds + 2 * 32 * BK); break;
+      conv_mfma_body<32, 64, true, UP, false>(p, bid, lds, lds + 2 * 32 * BK); break;
   }
 }
 
@@ -819,6 +849,37 @@ __global__ void pack_upfold_weight_kernel(const unsigned short* __restrict__ w,
   }
 }
 
+// two-source weight pack: 1x1 weights [Cout][Ca] and [Cout][Cb] -> one row
+// [Cout][Ca + Cb] per output channel, source 1 first, each branch's
+// per-channel scale (folded BN; absent = 1) multiplied in: float(w) *
+// scale[co], one fp32 multiply, rounded to bf16 once (round to nearest even).
+// The first Cout threads also write the fused shift shift_a + shift_b in
+// fp32 (absent = 0).
+__global__ void pack_cat_weight_kernel(const unsigned short* __restrict__ wa,
+                                       const unsigned short* __restrict__ wb,
+                                       const float* __restrict__ scale_a,
+                                       const float* __restrict__ scale_b,
+                                       const float* __restrict__ shift_a,
+                                       const float* __restrict__ shift_b,
+                                       unsigned short* __restrict__ out,
+                                       float* __restrict__ shift_out,
+                                       int Cout, int Ca, int Cb) {
+  const int K = Ca + Cb;
+  const long long total = (long long)Cout * K;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+       i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int k = (int)(i % K);
+    const int co = (int)(i / K);
+    const bool second = k >= Ca;
+    const unsigned short w = second ? wb[(long long)co * Cb + (k - Ca)]
+                                    : wa[(long long)co * Ca + k];
+    const float* scale = second ? scale_b : scale_a;
+    out[i] = f2us(us2f(w) * (scale ? scale[co] : 1.f));
+    if (i < Cout)
+      shift_out[i] = (shift_a ? shift_a[i] : 0.f) + (shift_b ? shift_b[i] : 0.f);
+  }
+}
+
 // weight pack: [Cout,Cin,KH,KW] (standard contiguous) -> fwd [Cout][f*Cin+ci]
 // and (optional) dgrad [Cin][(rot180 f)*Cout+co] in ONE pass. Weights change
 // every optimizer step, so the eager flip/permute/reshape chains re-ran per
@@ -889,6 +950,45 @@ void pack_upfold_weight(const Tensor& w, Tensor& out) {
                      (int)w.size(0), (int)w.size(1));
 }
 
+// Weight pack and fused shift of a two-source 1x1 conv: out [Cout][Ca + Cb]
+// bf16, shift_out [Cout] fp32 (pack_cat_weight_kernel). One launch.
+void pack_cat_weight(const Tensor& wa, const Tensor& wb,
+                     const OptTensor& scale_a, const OptTensor& scale_b,
+                     const OptTensor& shift_a, const OptTensor& shift_b,
+                     Tensor& out, Tensor& shift_out) {
+  for (const Tensor* w : {&wa, &wb})
+    TORCH_CHECK(w->is_cuda() && w->is_contiguous() && w->dim() == 4 &&
+                w->scalar_type() == at::ScalarType::BFloat16 &&
+                w->size(2) == 1 && w->size(3) == 1 && w->size(0) == wa.size(0),
+                "pack_cat_weight: contiguous bf16 [Cout][C][1][1] weights "
+                "with equal Cout");
+  const int64_t Cout = wa.size(0), Ca = wa.size(1), Cb = wb.size(1);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() &&
+              out.scalar_type() == at::ScalarType::BFloat16 &&
+              out.numel() == Cout * (Ca + Cb),
+              "pack_cat_weight: out must be bf16 [Cout][Ca+Cb]");
+  TORCH_CHECK(shift_out.is_cuda() && shift_out.is_contiguous() &&
+              shift_out.scalar_type() == at::ScalarType::Float &&
+              shift_out.numel() == Cout,
+              "pack_cat_weight: shift_out must be fp32 [Cout]");
+  auto vec = [&](const OptTensor& t) -> const float* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == at::ScalarType::Float &&
+                t->numel() == Cout,
+                "pack_cat_weight: scales and shifts must be fp32 [Cout]");
+    return t->data_ptr<float>();
+  };
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  dim3 grid(ibp::grid_1d(out.numel(), 256, 2048)), block(256);
+  hipLaunchKernelGGL(ibp::pack_cat_weight_kernel, grid, block, 0, stream,
+                     reinterpret_cast<const unsigned short*>(wa.data_ptr()),
+                     reinterpret_cast<const unsigned short*>(wb.data_ptr()),
+                     vec(scale_a), vec(scale_b), vec(shift_a), vec(shift_b),
+                     reinterpret_cast<unsigned short*>(out.data_ptr()),
+                     shift_out.data_ptr<float>(), (int)Cout, (int)Ca, (int)Cb);
+}
+
 namespace {
 
 using ibp::ConvPlan;
@@ -930,6 +1030,28 @@ ConvProblem make_problem(const Tensor& x, const Tensor& w_packed,
   return q;
 }
 
+// The second source of a two-source 1x1 conv: channels_last [N, Cin2, H, W]
+// over x's pixels. geom's Cin stays the first source's; the planner checks
+// the rest.
+void set_second_source(ConvProblem& q, const Tensor& x, const Tensor& x2,
+                       const Tensor& w_packed) {
+  ibp::ConvParams& p = q.p;
+  TORCH_CHECK(x2.is_cuda() && x2.device() == x.device() &&
+              x2.scalar_type() == at::ScalarType::BFloat16 && x2.dim() == 4 &&
+              x2.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+              x2.size(0) == p.N && x2.size(2) == p.H && x2.size(3) == p.W,
+              "conv_mfma: x2 must be channels_last bf16 [N, Cin2, H, W]");
+  TORCH_CHECK(x.dim() == 4 &&
+              x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+              x.size(0) == p.N && x.size(1) == p.Cin && x.size(2) == p.H &&
+              x.size(3) == p.W,
+              "conv_mfma: with x2, x must be channels_last [N, Cin, H, W]");
+  p.Cin2 = (int)x2.size(1);
+  p.x2 = reinterpret_cast<const unsigned short*>(x2.data_ptr());
+  TORCH_CHECK(w_packed.numel() == (int64_t)p.Cout * (p.Cin + p.Cin2),
+              "conv_mfma: two-source pack must be [Cout][Cin + Cin2]");
+}
+
 Tensor alloc_output(ConvProblem& q, const Tensor& x) {
   Tensor y = torch::empty({q.p.N, q.p.Ho, q.p.Wo, q.p.Cout}, x.options());
   q.p.y = reinterpret_cast<unsigned short*>(y.data_ptr());
@@ -961,10 +1083,12 @@ void launch_single(const ConvPlan& plan, hipStream_t stream) {
   const ibp::ConvParams& p = plan.p;
   TORCH_CHECK(!p.up, "upfold plans launch through the grouped kernel");
   with_tile(plan, [&](auto bm, auto bn, auto deep) {
-    hipLaunchKernelGGL(
-        (ibp::conv_mfma_kernel<decltype(bm)::value, decltype(bn)::value,
-                               decltype(deep)::value>),
-        dim3(plan.nblocks), dim3(256), 0, stream, p);
+    with_flag(p.Cin2 != 0, [&](auto cat) {
+      hipLaunchKernelGGL(
+          (ibp::conv_mfma_kernel<decltype(bm)::value, decltype(bn)::value,
+                                 decltype(deep)::value, decltype(cat)::value>),
+          dim3(plan.nblocks), dim3(256), 0, stream, p);
+    });
   });
   if (p.splitk > 1)
     with_flag(plan.vec_combine, [&](auto vec) {
@@ -1018,9 +1142,11 @@ Tensor conv_mfma_fwd(const Tensor& x, const Tensor& w_packed,
                      const std::vector<int64_t>& geom, const OptTensor& scale,
                      const OptTensor& shift, const OptTensor& residual,
                      bool act, const OptTensor& residual_post,
-                     const OptTensor& residual_post2) {
+                     const OptTensor& residual_post2, const OptTensor& x2) {
   ConvProblem q = make_problem(x, w_packed, geom, scale, shift, residual, act,
                                residual_post, residual_post2);
+  // two-source 1x1 conv: K = Cin + Cin2, w_packed [Cout][Cin + Cin2]
+  if (x2.has_value()) set_second_source(q, x, *x2, w_packed);
   Tensor y = alloc_output(q, x);
   std::vector<ConvPlan> plans{ibp::plan_conv(q)};
   run_plans(plans, at::hip::getCurrentHIPStream().stream(),

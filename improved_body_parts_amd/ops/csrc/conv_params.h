@@ -34,6 +34,11 @@ struct ConvParams {
   // LOW-resolution Ho x Wo grid and row (n, i, j) is stored at pixel
   // (n*2Ho + 2i+py)*2Wo + 2j+px of y / res / res_post / res_post2
   int up, py, px;
+  // second source of a two-source 1x1 conv (Cin2 = 0: off): K = Cin + Cin2,
+  // row m reads x[m*Cin + k] for k < Cin and x2[m*Cin2 + (k - Cin)] past it.
+  // The host requires Cin % BK == 0, so a K-chunk never straddles the two.
+  int Cin2;
+  const unsigned short* x2;  // [M][Cin2] bf16
 };
 
 // grouped launch: up to kMaxGroup INDEPENDENT convs in one grid

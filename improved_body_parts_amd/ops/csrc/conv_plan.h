@@ -122,6 +122,29 @@ inline ConvPlan plan_conv(const ConvProblem& q) {
   // any Cin is legal: subpieces crossing tap boundaries take the per-element
   // re-derive path (the Cin=3 stem runs there; Cin % 8 == 0 stays vectorized)
   p.K = p.KH * p.KW * p.Cin;
+  if (p.x2 != nullptr || p.Cin2 != 0) {
+    // two-source 1x1 conv: planned like any conv over K = Cin + Cin2. Source
+    // 1 must fill whole K-chunks (the kernel picks the source per chunk) and
+    // the gather has no tap walk, so only the plain 1x1 geometry is legal.
+    if (p.x2 == nullptr || p.Cin2 <= 0)
+      throw std::invalid_argument(
+          "two-source conv: x2 and Cin2 > 0 go together");
+    if (p.Cin <= 0 || p.Cin % BK != 0)
+      throw std::invalid_argument(
+          "two-source conv: Cin must be a multiple of 64");
+    if (p.KH * p.KW != 1 || p.stride != 1 || p.pad_h != 0 || p.pad_w != 0 ||
+        p.dil_h != 1 || p.dil_w != 1 || p.zs != 1 || p.Ho != p.H ||
+        p.Wo != p.W)
+      throw std::invalid_argument(
+          "two-source conv: 1x1, stride 1, unpadded, undilated, zs 1 only");
+    if (p.up)
+      throw std::invalid_argument(
+          "two-source conv: cannot be an upfold parity");
+    if (q.tile)
+      throw std::invalid_argument(
+          "two-source conv: plans its own tile");
+    p.K = p.Cin + p.Cin2;
+  }
   const TilePlan t = q.tile ? *q.tile : plan_tile(p.M, p.Cout, p.K);
   const int Cout = p.Cout, splitk = t.splitk;
   p.n_mtiles = t.n_mtiles;
@@ -212,6 +235,10 @@ inline GroupPlan assemble_group(std::vector<ConvPlan>& plans, size_t first,
     if ((plan.p.up != 0) != gp.up)
       throw std::invalid_argument(
           "grouped conv: upfold and plain members cannot mix");
+    // the grouped kernels are compiled without the two-source gather
+    if (plan.p.Cin2 != 0)
+      throw std::invalid_argument(
+          "grouped conv: a two-source conv launches on its own");
     gp.order[i] = i;
     gp.ws_off[i] = ws_total;
     if (plan.ws_elems > 0) set_workspace(plan, ws_base + ws_total);
