@@ -79,6 +79,9 @@ std::vector<Tensor> conv_mfma_fwd_grouped(
     const std::vector<c10::optional<Tensor>>& residual_post2s);
 
 std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K);
+std::vector<int64_t> conv_mfma_conv_plan(const Tensor& x,
+                                         const Tensor& w_packed,
+                                         const std::vector<int64_t>& geom);
 
 void pack_conv_weight(const Tensor& w, Tensor& fwd_pack,
                       const c10::optional<Tensor>& dgrad_pack);
@@ -181,6 +184,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_mfma_tile_plan", &conv_mfma_tile_plan,
         "debug: [BM, BN, splitk, deep] planned for GEMM extents (M, Cout, K)",
         py::arg("M"), py::arg("Cout"), py::arg("K"));
+  m.def("conv_mfma_conv_plan", &conv_mfma_conv_plan,
+        "debug: [BM, BN, splitk, deep, gather] planned for conv_mfma_fwd(x, "
+        "w_packed, geom); gather 1 = tap-uniform, 0 = generic",
+        py::arg("x"), py::arg("w_packed"), py::arg("geom"));
   m.def("pack_conv_weight", &pack_conv_weight,
         "fwd + dgrad weight packs in one kernel",
         py::arg("w"), py::arg("fwd_pack"), py::arg("dgrad_pack") = c10::nullopt);

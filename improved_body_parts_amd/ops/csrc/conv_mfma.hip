@@ -29,6 +29,18 @@
 //     summed weights (pack_upfold_weight_kernel); each parity's rows are
 //     stored at its own pixels of the full-resolution output
 //     (conv_mfma_upfold_fwd).
+//   * two gathers fill the same LDS image. The generic one (below) handles any
+//     shape and re-derives addresses, bounds, alignment and K-tail per chunk.
+//     The tap-uniform one (TU, ConvParams::gather == 1, chosen by the host
+//     planner: one source, zs == 1, Cin % 64 == 0, <= 32 taps, 16-byte
+//     aligned x and w, 32-bit rows and byte offsets) computes a row's pixel
+//     offset and in-bounds tap mask once per block, walks (kh, kw, ci) in
+//     scalar registers, and loads full 128-byte lines (8 lanes x 16 bytes per
+//     row) through range-checked buffer loads; padding taps and rows past
+//     M / Cout select an out-of-range offset and read zeros. Its main loop
+//     has no division, no 64-bit multiply and no branch but its own. Chunk
+//     boundaries, fragment layout and MFMA order are shared, so both gathers
+//     give the same bits (IBP_CONV_GATHER=0 forces the generic one).
 //
 // Supported: any KHxKW with Cin % 8 == 0 (per-8 subpieces re-derive their
 // filter tap, so Cin 16 s2d-stem tiles and 64..768 hourglass tiles both hit
@@ -74,7 +86,8 @@ __device__ __forceinline__ int lds_off(int row, int k) {
 //
 // CAT compiles the two-source 1x1 gather of ConvParams::x2 in (and the tap
 // walk out); only conv_mfma_kernel<.., true> instantiates it.
-template <int BM, int BN, bool DEEP, bool UP, bool CAT, typename Params>
+template <int BM, int BN, bool DEEP, bool UP, bool CAT, bool TU,
+          typename Params>
 __device__ __forceinline__ void conv_mfma_body(const Params& p,
                                                const int bid,
                                                unsigned short* lds_a,
@@ -311,6 +324,127 @@ a_done:
     }
   };
 
+  // ---- tap-uniform gather (TU; ConvParams::gather == 1) ---------------------
+  // The planner guarantees Cin % BK == 0 (a K-chunk lies inside ONE filter tap,
+  // the same for the whole block), no K-tail, zs == 1, m32, 16-byte aligned x
+  // and w, and both operands addressable with unsigned 32-bit byte offsets.
+  // Staging map: a 16-byte piece per lane, eight consecutive lanes cover one
+  // row's 128 bytes of the chunk (full lines), a thread's pieces lie 32 rows
+  // apart. The LDS image is the generic one.
+  //   per row, once:   byte offset of pixel (n, ho*stride - pad_h,
+  //                    wo*stride - pad_w) plus the lane's piece (may be
+  //                    "negative": unsigned wrap-around, exact once an
+  //                    in-bounds tap is added), and a bit per tap that is in
+  //                    bounds for the row (0 for rows past M)
+  //   per block:       (kh, kw, ci) in scalar registers, walked by BK
+  //   per chunk/piece: one add, one bit test, one select, the 16-byte load
+  // Padding taps and rows past M / Cout select the offset kGatherOob, which
+  // the buffer's range check answers with zeros: no branch, no zero fill.
+  constexpr int A_PIECES = A_ELEMS / 8;
+  constexpr int B_PIECES = B_ELEMS / 8;
+  typedef unsigned int uintv4 __attribute__((ext_vector_type(4)));
+  const int g_row = tid >> 3;          // rows g_row + 32 * j
+  const int g_k = (tid & 7) * 8;       // the lane's piece of the chunk
+  unsigned tu_abase[TU ? A_PIECES : 1];
+  unsigned tu_amask[TU ? A_PIECES : 1];
+  unsigned tu_boff[TU ? B_PIECES : 1];
+  int tu_ci = 0, tu_kh = 0, tu_kw = 0;  // block-uniform tap of the next chunk
+  unsigned tu_bk = 0;                   // byte offset of that chunk in a w row
+  unsigned tu_dh = 0, tu_dw = 0;        // bytes per kh / kw step
+  // range-checked views of x and w, exactly as long as the operands (the
+  // type has no empty value; without TU nothing uses them and they compile
+  // away)
+  const unsigned pix = (unsigned)p.Cin * 2u;   // bytes per pixel
+  const __amdgpu_buffer_rsrc_t tu_xbuf = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned short*>(p.x), 0,
+      (int)((unsigned)p.N * (unsigned)p.H * (unsigned)p.W * pix), 0x00020000);
+  const __amdgpu_buffer_rsrc_t tu_wbuf = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned short*>(p.w), 0,
+      (int)((unsigned)p.Cout * (unsigned)p.K * 2u), 0x00020000);
+  if constexpr (TU) {
+    tu_dh = (unsigned)(p.dil_h * p.W) * pix;
+    tu_dw = (unsigned)p.dil_w * pix;
+    const int kk0 = k_begin * BK;
+    const int f0 = kk0 / p.Cin;
+    tu_ci = kk0 - f0 * p.Cin;
+    tu_kh = f0 / p.KW;
+    tu_kw = f0 - tu_kh * p.KW;
+    tu_bk = (unsigned)kk0 * 2u;
+    // the first row is decomposed once, the others carry-walk from it
+    unsigned t = (unsigned)m0 + (unsigned)g_row;
+    int wo = (int)(t % (unsigned)p.Wo); t /= (unsigned)p.Wo;
+    int ho = (int)(t % (unsigned)p.Ho);
+    int n = (int)(t / (unsigned)p.Ho);
+    #pragma unroll
+    for (int j = 0; j < A_PIECES; ++j) {
+      const int hb = ho * p.stride - p.pad_h;
+      const int wb = wo * p.stride - p.pad_w;
+      unsigned colm = 0, mask = 0;
+      for (int kw = 0; kw < p.KW; ++kw)
+        if ((unsigned)(wb + kw * p.dil_w) < (unsigned)p.W) colm |= 1u << kw;
+      for (int kh = 0; kh < p.KH; ++kh)
+        if ((unsigned)(hb + kh * p.dil_h) < (unsigned)p.H)
+          mask |= colm << (kh * p.KW);
+      tu_amask[j] = (m0 + g_row + 32 * j < p.M) ? mask : 0u;
+      tu_abase[j] =
+          (((unsigned)n * (unsigned)p.H + (unsigned)hb) * (unsigned)p.W +
+           (unsigned)wb) * pix + (unsigned)g_k * 2u;
+      wo += 32;
+      while (wo >= p.Wo) {
+        wo -= p.Wo;
+        if (++ho == p.Ho) { ho = 0; ++n; }
+      }
+    }
+    #pragma unroll
+    for (int j = 0; j < B_PIECES; ++j) {
+      const int col = n0 + g_row + 32 * j;
+      tu_boff[j] = col < p.Cout
+          ? (unsigned)col * (unsigned)p.K * 2u + (unsigned)g_k * 2u
+          : kGatherOob;
+    }
+  }
+  // stage the NEXT sequential chunk (TU): the tap state walks forward
+  auto load_chunk_tu = [&](unsigned short (&a_reg)[A_ELEMS],
+                           unsigned short (&b_reg)[B_ELEMS]) {
+    const unsigned tap = (unsigned)tu_kh * tu_dh + (unsigned)tu_kw * tu_dw +
+                         (unsigned)tu_ci * 2u;
+    const unsigned bit = 1u << (tu_kh * p.KW + tu_kw);
+    #pragma unroll
+    for (int j = 0; j < A_PIECES; ++j) {
+      const unsigned off =
+          (tu_amask[j] & bit) ? tu_abase[j] + tap : kGatherOob;
+      *reinterpret_cast<uintv4*>(&a_reg[j * 8]) =
+          __builtin_amdgcn_raw_buffer_load_b128(tu_xbuf, (int)off, 0, 0);
+    }
+    #pragma unroll
+    for (int j = 0; j < B_PIECES; ++j)
+      *reinterpret_cast<uintv4*>(&b_reg[j * 8]) =
+          __builtin_amdgcn_raw_buffer_load_b128(tu_wbuf, (int)tu_boff[j],
+                                                (int)tu_bk, 0);
+    // scalar walk to the next chunk (selects, no branch)
+    tu_bk += BK * 2u;
+    tu_ci += BK;
+    const bool tap_end = tu_ci >= p.Cin;
+    tu_ci = tap_end ? 0 : tu_ci;
+    tu_kw += tap_end ? 1 : 0;
+    const bool row_end = tu_kw >= p.KW;
+    tu_kw = row_end ? 0 : tu_kw;
+    tu_kh += row_end ? 1 : 0;
+  };
+  auto write_chunk_tu = [&](int buf, unsigned short (&a_reg)[A_ELEMS],
+                            unsigned short (&b_reg)[B_ELEMS]) {
+    #pragma unroll
+    for (int j = 0; j < A_PIECES; ++j)
+      *reinterpret_cast<ushortv8*>(
+          &lds_a[buf * (BM * BK) + lds_off(g_row + 32 * j, g_k)]) =
+          *reinterpret_cast<const ushortv8*>(&a_reg[j * 8]);
+    #pragma unroll
+    for (int j = 0; j < B_PIECES; ++j)
+      *reinterpret_cast<ushortv8*>(
+          &lds_b[buf * (BN * BK) + lds_off(g_row + 32 * j, g_k)]) =
+          *reinterpret_cast<const ushortv8*>(&b_reg[j * 8]);
+  };
+
   auto write_chunk = [&](int buf, unsigned short (&a_reg)[A_ELEMS],
                          unsigned short (&b_reg)[B_ELEMS]) {
     #pragma unroll
@@ -350,7 +484,37 @@ a_done:
   };
 
   // ---- main loop: register-staged double buffer ----------------------------
-  if constexpr (DEEP) {
+  if constexpr (TU && DEEP) {
+    // the DEEP schedule below with the tap-uniform gather
+    load_chunk_tu(a_reg0, b_reg0);
+    write_chunk_tu(0, a_reg0, b_reg0);
+    if (nk > 1) load_chunk_tu(a_reg1, b_reg1);
+    __syncthreads();
+    for (int t = 0; t < nk; ++t) {
+      if (t + 2 < nk) load_chunk_tu(a_reg0, b_reg0);
+      compute(0);
+      if (t + 1 < nk) write_chunk_tu(1, a_reg1, b_reg1);
+      __syncthreads();
+      if (++t >= nk) break;
+      if (t + 2 < nk) load_chunk_tu(a_reg1, b_reg1);
+      compute(1);
+      if (t + 1 < nk) write_chunk_tu(0, a_reg0, b_reg0);
+      __syncthreads();
+    }
+  } else if constexpr (TU) {
+    // the single-stage schedule below with its last step peeled off, so the
+    // loop body holds no test of its own: load t+1, MFMA t, write t+1, barrier
+    load_chunk_tu(a_reg0, b_reg0);
+    write_chunk_tu(0, a_reg0, b_reg0);
+    __syncthreads();
+    for (int t = 0; t + 1 < nk; ++t) {
+      load_chunk_tu(a_reg0, b_reg0);
+      compute(t & 1);
+      write_chunk_tu((t + 1) & 1, a_reg0, b_reg0);
+      __syncthreads();
+    }
+    compute((nk - 1) & 1);
+  } else if constexpr (DEEP) {
     // 2-deep prefetch: chunk t+2's loads issue at iteration t, land at t+1
     load_chunk(k_begin, a_reg0, b_reg0);
     write_chunk(0, a_reg0, b_reg0);
@@ -589,11 +753,14 @@ a_done:
   }
 }
 
-template <int BM, int BN, bool DEEP = false, bool CAT = false>
+// TU compiles the tap-uniform gather in instead of the generic one; the host
+// launches it for plans with ConvParams::gather == 1 (never with CAT).
+template <int BM, int BN, bool DEEP = false, bool CAT = false, bool TU = false>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvParams p) {
+  static_assert(!(CAT && TU), "the two-source conv keeps its own gather");
   __shared__ unsigned short lds_a[2 * BM * BK];
   __shared__ unsigned short lds_b[2 * BN * BK];
-  conv_mfma_body<BM, BN, DEEP, false, CAT>(p, blockIdx.x, lds_a, lds_b);
+  conv_mfma_body<BM, BN, DEEP, false, CAT, TU>(p, blockIdx.x, lds_a, lds_b);
 }
 
 // ---- grouped launch --------------------------------------------------------
@@ -634,24 +801,29 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_grouped_kernel(
   const auto& p = *(kernarg_params)(ka + offsetof(ConvGroupParams, p) +
                                     (size_t)pi * sizeof(ConvParams));
   const int bid = gb - base;
-  switch (cfg) {
-    case tile_cfg(128, 128, false):
-      conv_mfma_body<128, 128, false, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
-    case tile_cfg(128, 128, true):
-      conv_mfma_body<128, 128, true, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
-    case tile_cfg(128, 64, false):
-      conv_mfma_body<128, 64, false, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
-    case tile_cfg(128, 64, true):
-      conv_mfma_body<128, 64, true, UP, false>(p, bid, lds, lds + 2 * 128 * BK); break;
-    case tile_cfg(64, 64, false):
-      conv_mfma_body<64, 64, false, UP, false>(p, bid, lds, lds + 2 * 64 * BK); break;
-    case tile_cfg(64, 64, true):
-      conv_mfma_body<64, 64, true, UP, false>(p, bid, lds, lds + 2 * 64 * BK); break;
-    case tile_cfg(32, 64, false):
-      conv_mfma_body<32, 64, false, UP, false>(p, bid, lds, lds + 2 * 32 * BK); break;
-    default:
-      conv_mfma_body<32, 64, true, UP, false>(p, bid, lds, lds + 2 * 32 * BK); break;
+  // the member's gather (ConvParams::gather) rides above the cfg bits
+  #define IBP_BODY(BM_, BN_, DEEP_, TU_)                                     \
+    conv_mfma_body<BM_, BN_, DEEP_, UP, false, TU_>(p, bid, lds,            \
+                                                    lds + 2 * BM_ * BK)
+  switch (cfg | (p.gather ? 8 : 0)) {
+    case tile_cfg(128, 128, false): IBP_BODY(128, 128, false, false); break;
+    case tile_cfg(128, 128, true): IBP_BODY(128, 128, true, false); break;
+    case tile_cfg(128, 64, false): IBP_BODY(128, 64, false, false); break;
+    case tile_cfg(128, 64, true): IBP_BODY(128, 64, true, false); break;
+    case tile_cfg(64, 64, false): IBP_BODY(64, 64, false, false); break;
+    case tile_cfg(64, 64, true): IBP_BODY(64, 64, true, false); break;
+    case tile_cfg(32, 64, false): IBP_BODY(32, 64, false, false); break;
+    case tile_cfg(32, 64, true): IBP_BODY(32, 64, true, false); break;
+    case 8 | tile_cfg(128, 128, false): IBP_BODY(128, 128, false, true); break;
+    case 8 | tile_cfg(128, 128, true): IBP_BODY(128, 128, true, true); break;
+    case 8 | tile_cfg(128, 64, false): IBP_BODY(128, 64, false, true); break;
+    case 8 | tile_cfg(128, 64, true): IBP_BODY(128, 64, true, true); break;
+    case 8 | tile_cfg(64, 64, false): IBP_BODY(64, 64, false, true); break;
+    case 8 | tile_cfg(64, 64, true): IBP_BODY(64, 64, true, true); break;
+    case 8 | tile_cfg(32, 64, false): IBP_BODY(32, 64, false, true); break;
+    default: IBP_BODY(32, 64, true, true); break;
   }
+  #undef IBP_BODY
 }
 
 // The grouped kernel reads its table at offset 0 of the kernel-argument
@@ -1083,11 +1255,18 @@ void launch_single(const ConvPlan& plan, hipStream_t stream) {
   const ibp::ConvParams& p = plan.p;
   TORCH_CHECK(!p.up, "upfold plans launch through the grouped kernel");
   with_tile(plan, [&](auto bm, auto bn, auto deep) {
+    // the planner never sets the tap-uniform gather on a two-source conv
+    TORCH_CHECK(!(p.Cin2 != 0 && p.gather != 0));
     with_flag(p.Cin2 != 0, [&](auto cat) {
-      hipLaunchKernelGGL(
-          (ibp::conv_mfma_kernel<decltype(bm)::value, decltype(bn)::value,
-                                 decltype(deep)::value, decltype(cat)::value>),
-          dim3(plan.nblocks), dim3(256), 0, stream, p);
+      with_flag(p.gather != 0, [&](auto tu) {
+        if constexpr (!(decltype(cat)::value && decltype(tu)::value))
+          hipLaunchKernelGGL(
+              (ibp::conv_mfma_kernel<decltype(bm)::value, decltype(bn)::value,
+                                     decltype(deep)::value,
+                                     decltype(cat)::value,
+                                     decltype(tu)::value>),
+              dim3(plan.nblocks), dim3(256), 0, stream, p);
+      });
     });
   });
   if (p.splitk > 1)
@@ -1247,6 +1426,20 @@ Tensor conv_mfma_upfold_fwd(const Tensor& x_low, const Tensor& packs,
 std::vector<int64_t> conv_mfma_tile_plan(int64_t M, int64_t Cout, int64_t K) {
   const ibp::TilePlan t = ibp::plan_tile(M, (int)Cout, (int)K);
   return {t.BM, t.BN, t.splitk, t.deep ? 1 : 0};
+}
+
+// {BM, BN, splitk, deep, gather} of the plan that conv_mfma_fwd(x, w_packed,
+// geom, ...) runs: the gather depends on the operands' addresses as well as
+// on the geometry (conv_plan.h, gather_eligible). Launches nothing.
+std::vector<int64_t> conv_mfma_conv_plan(const Tensor& x,
+                                         const Tensor& w_packed,
+                                         const std::vector<int64_t>& geom) {
+  const ConvProblem q =
+      make_problem(x, w_packed, geom, c10::nullopt, c10::nullopt, c10::nullopt,
+                   false, c10::nullopt, c10::nullopt);
+  const ConvPlan plan = ibp::plan_conv(q);
+  return {plan.t.BM, plan.t.BN, plan.p.splitk, plan.t.deep ? 1 : 0,
+          plan.p.gather};
 }
 
 // {BM, BN, splitk, deep} shared by the four parities of an upfold conv over

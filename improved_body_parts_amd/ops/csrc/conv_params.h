@@ -39,7 +39,19 @@ struct ConvParams {
   // The host requires Cin % BK == 0, so a K-chunk never straddles the two.
   int Cin2;
   const unsigned short* x2;  // [M][Cin2] bf16
+  // A/B gather of the main loop: 0 = generic (any shape), 1 = tap-uniform
+  // (plan_conv sets it; its conditions are listed there)
+  int gather;
 };
+
+// The tap-uniform gather addresses x and w through range-checked buffer
+// loads with UNSIGNED 32-BIT BYTE offsets: both operands must be at most
+// kGatherMaxBytes long (plan_conv enforces it), so that every in-range offset
+// lies below kGatherOob, the offset the kernel substitutes for a padding tap
+// or a row past M / Cout — it is past the end of any such buffer and the
+// load returns zeros.
+constexpr long long kGatherMaxBytes = 0x7fffffffLL;
+constexpr unsigned kGatherOob = 0x80000000u;
 
 // grouped launch: up to kMaxGroup INDEPENDENT convs in one grid
 constexpr int kMaxGroup = 8;

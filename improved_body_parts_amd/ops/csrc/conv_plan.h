@@ -114,6 +114,30 @@ inline TilePlan plan_upfold_tile(long long M_low, int Cout, int Cin) {
   return plan_tiles(M_low, Cout, 4 * Cin, 4);
 }
 
+// Tap-uniform gather (ConvParams::gather = 1), decided from the finished
+// geometry, K, m32 and the x / w pointers. All of:
+//   * one source, zs == 1 (no virtual zero-dilated image);
+//   * Cin % BK == 0: a K-chunk lies inside one filter tap, so the tap is the
+//     same for the whole block, and K % BK == 0: no K-tail;
+//   * KH*KW <= 32: a row's in-bounds taps are one 32-bit mask;
+//   * x and w 16-byte aligned: with Cin % 64 == 0 every 16-byte piece is;
+//   * m32: rows decompose in 32-bit math;
+//   * x and w at most kGatherMaxBytes long: the kernel's offsets are unsigned
+//     32-bit byte offsets into range-checked buffers (conv_params.h).
+// IBP_CONV_GATHER=0 forces the generic gather everywhere (A/B switch).
+inline bool gather_eligible(const ConvParams& p) {
+  if (const char* e = getenv("IBP_CONV_GATHER"))
+    if (e[0] == '0' && e[1] == '\0') return false;
+  if (p.x2 != nullptr || p.Cin2 != 0 || p.zs != 1) return false;
+  if (p.Cin <= 0 || p.Cin % BK != 0) return false;
+  if (p.KH * p.KW < 1 || p.KH * p.KW > 32) return false;
+  if (misaligned(p.x, 16) || misaligned(p.w, 16)) return false;
+  if (!p.m32) return false;
+  const long long x_bytes = 2LL * p.N * p.H * p.W * p.Cin;
+  const long long w_bytes = 2LL * p.Cout * p.K;
+  return x_bytes <= kGatherMaxBytes && w_bytes <= kGatherMaxBytes;
+}
+
 inline ConvPlan plan_conv(const ConvProblem& q) {
   ConvPlan plan;
   plan.p = q.p;
@@ -176,6 +200,7 @@ inline ConvPlan plan_conv(const ConvProblem& q) {
   if (p.up && 4 * p.M + 4 * t.BM >= (1LL << 31))
     throw std::invalid_argument(
         "upfold conv: output too large for 32-bit row math");
+  p.gather = gather_eligible(p) ? 1 : 0;
   plan.t = t;
   plan.nblocks = t.ntiles * splitk;
   return plan;
