@@ -83,6 +83,15 @@ class RawDataIterator:
             mask_all = np.ones(img.shape[:2], np.float32)
         return img, mask_miss, mask_all, meta
 
+    def raw(self, index):
+        """The first half of ``gen``: one record, read and converted to the
+        canonical joint order, with no transform applied."""
+        self._ensure_open()
+        key = self.keys[index % len(self.keys)]
+        img, mask_miss, mask_all, meta = self.read_data(key)
+        meta = self.source_config.convert(meta, self.global_config)
+        return img, mask_miss, mask_all, meta
+
     def gen(self, index):
         self._ensure_open()
         key = self.keys[index % len(self.keys)]
@@ -111,6 +120,141 @@ class MyDataset(Dataset):
 
     def __getitem__(self, index):
         return self.iterator.gen(index)
+
+
+class DeviceAugmentLoader:
+    """Real-data training stream with augmentation and GT on the device.
+
+    Per batch the host reads the raw records, draws one ``AugmentSelection``
+    per sample, moves the joints and packs the uint8 sources; the affine warp
+    (ops/csrc/augment.hip) and the ground truth (ops/csrc/heatmap_gt.hip) run
+    on the GPU. Same contract as ``DeviceGTSyntheticLoader``: iterable
+    yielding ``(images (B,H,W,3), mask_miss (B,1,h,w), heatmaps (B,C,h,w))``
+    on ``device`` in ``dtype``. On a CPU device the same stream is produced by
+    the host ``Transformer`` and ``Heatmapper``.
+
+    ``dataset`` is a ``MyDataset`` (anything with ``__len__`` and
+    ``.iterator.raw``). Ranks take a strided share of the epoch's index list.
+    """
+
+    def __init__(self, dataset, batch_size: int, device="cuda",
+                 dtype=torch.float32, augment=True, shuffle=True, seed=0,
+                 rank=0, world_size=1, drop_last=True):
+        from .device_transform import DeviceTransformer
+        self.dataset = dataset
+        self.iterator = dataset.iterator
+        self.config = self.iterator.global_config
+        self.batch_size = batch_size
+        self.device = torch.device(device)
+        self.dtype = dtype
+        self.augment = augment
+        self.shuffle = shuffle
+        self.seed = seed
+        self.rank = rank
+        self.world_size = world_size
+        self.drop_last = drop_last
+        self.transformer = DeviceTransformer(self.config, self.device, dtype)
+        self._epoch = 0
+
+    def set_epoch(self, epoch: int):
+        self._epoch = epoch
+
+    def epoch_indices(self):
+        """This rank's share of the current epoch's (shuffled) index list."""
+        n = len(self.dataset)
+        if self.shuffle:
+            order = np.random.default_rng(
+                self.seed * 1_000_003 + self._epoch).permutation(n)
+        else:
+            order = np.arange(n)
+        share = order[self.rank::self.world_size]
+        if self.drop_last:
+            # every rank takes the same number of steps
+            share = share[:n // self.world_size]
+        return share
+
+    def __len__(self):
+        n = len(self.epoch_indices())
+        if self.drop_last:
+            return n // self.batch_size
+        return (n + self.batch_size - 1) // self.batch_size
+
+    def _host_batch(self, indices, rng):
+        """The host side of one batch: records, draws, joints, packing."""
+        records = [self.iterator.raw(int(i)) for i in indices]
+        augs = None if self.augment else [AugmentSelection.unrandom()
+                                          for _ in records]
+        return self.transformer.prepare(records, augs, rng)
+
+    def _pad_joints(self, joints):
+        people = max(max(len(j) for j in joints), 1)
+        out = np.zeros((len(joints), people, self.config.num_parts, 3), np.float32)
+        out[..., 2] = 2.0   # vis = 2: absent
+        for b, j in enumerate(joints):
+            out[b, :len(j)] = j
+        return out
+
+    def __iter__(self):
+        import queue
+        import random
+        import threading
+        share = self.epoch_indices()
+        steps = len(self)
+        rng = random.Random((self.seed * 7_777_777 + self._epoch) * 4099 + self.rank)
+
+        # record reading, draws and packing run one batch ahead in a producer
+        # thread, overlapping the GPU step (as in DeviceGTSyntheticLoader)
+        q: queue.Queue = queue.Queue(maxsize=2)
+        stop = threading.Event()
+
+        def put(item):
+            # gives up when the consumer has left (an epoch cut short)
+            while not stop.is_set():
+                try:
+                    q.put(item, timeout=0.1)
+                    return True
+                except queue.Full:
+                    pass
+            return False
+
+        def produce():
+            try:
+                for s in range(steps):
+                    idx = share[s * self.batch_size:(s + 1) * self.batch_size]
+                    if not put(self._host_batch(idx, rng)):
+                        return
+                put(None)
+            except BaseException as e:  # surface reader errors in the consumer
+                put(e)
+
+        t = threading.Thread(target=produce, daemon=True)
+        t.start()
+        try:
+            while True:
+                item = q.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                yield self._device_batch(item)
+        finally:
+            stop.set()
+
+    def _device_batch(self, prepared):
+        """The device side of one batch: H2D + warp, then GT."""
+        from .heatmapper import create_heatmaps_device
+        images, mask_miss, mask_all, joints = self.transformer.execute(prepared)
+        if self.device.type == "cuda":
+            heatmaps = create_heatmaps_device(
+                self._pad_joints(joints), mask_all, self.config,
+                device=self.device)
+        else:
+            hm = self.iterator.heatmapper
+            heatmaps = torch.from_numpy(np.stack([
+                hm.create_heatmaps(j, m) for j, m in
+                zip(joints, mask_all.numpy())]))
+        return (images, mask_miss[:, None].to(self.dtype),
+                heatmaps.to(self.dtype))
 
 
 def build_coco_h5(ann_file: str, img_dir: str, out_path: str, image_size: int = 512):

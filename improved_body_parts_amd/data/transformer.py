@@ -70,6 +70,22 @@ class AugmentSelection:
         return m
 
 
+def transform_joints(joints, M, flip, config):
+    """Joints through the image's affine as homogeneous points, then the
+    left/right part-id swap of a horizontal flip (reference :173-177).
+    Shared by the host ``Transformer`` and the device-side path."""
+    joints = np.array(joints, dtype=np.float32, copy=True)
+    pts = np.concatenate([joints[:, :, 0:2],
+                          np.ones(joints.shape[:2] + (1,), np.float32)], axis=2)
+    joints[:, :, 0:2] = pts @ M.T
+    if flip:
+        order = np.arange(config.num_parts)
+        for l, r in zip(config.leftParts, config.rightParts):
+            order[l], order[r] = r, l
+        joints = joints[:, order, :]
+    return joints
+
+
 class Transformer:
     def __init__(self, config):
         self.config = config
@@ -89,30 +105,26 @@ class Transformer:
         center = np.asarray(meta["objpos"], dtype=np.float32).reshape(2)
         M = aug.affine(center, scale_self, cfg)
 
+        meta = dict(meta)
+        meta["joints"] = transform_joints(meta["joints"], M, aug.flip, cfg)
+        tint = self._tint_params(rng) if aug.tint and np.ndim(img) == 3 else None
+        img, mask_miss, mask_all = self.warp(img, mask_miss, mask_all, M, tint)
+        return img, mask_miss, mask_all, meta
+
+    def warp(self, img, mask_miss, mask_all, M, tint=None):
+        """The pixel half of ``transform``: warp image and masks by ``M``
+        (source -> destination), tint with ``tint = (gains, shift)`` if given,
+        pool the masks to the stride grid (reference :178-183)."""
+        cfg = self.config
         img = self._warp(img, M, (cfg.height, cfg.width), order=1,
                          cval=float(np.mean((128,))))
         mask_miss = self._warp(self._to_float01(mask_miss), M, (cfg.height, cfg.width),
                                order=1, cval=1.0)
         mask_all = self._warp(self._to_float01(mask_all), M, (cfg.height, cfg.width),
                               order=1, cval=0.0)
+        if tint is not None:
+            img = self._apply_tint(img, *tint)
 
-        joints = np.array(meta["joints"], dtype=np.float32, copy=True)
-        pts = np.concatenate([joints[:, :, 0:2],
-                              np.ones(joints.shape[:2] + (1,), np.float32)], axis=2)
-        joints[:, :, 0:2] = pts @ M.T
-        if aug.flip:
-            # swap left/right part ids (reference :173-177)
-            order = np.arange(cfg.num_parts)
-            for l, r in zip(cfg.leftParts, cfg.rightParts):
-                order[l], order[r] = r, l
-            joints = joints[:, order, :]
-        meta = dict(meta)
-        meta["joints"] = joints
-
-        if aug.tint and img.ndim == 3:
-            img = self._tint(img, rng)
-
-        # masks live on the stride-grid (reference :178-183)
         s = cfg.stride
         mask_miss = self._area_pool(mask_miss, s)
         mask_all = self._area_pool(mask_all, s)
@@ -120,7 +132,7 @@ class Transformer:
         img = np.ascontiguousarray(img, dtype=np.float32)
         if img.max() > 1.5:
             img = img / 255.0
-        return img, mask_miss.astype(np.float32), mask_all.astype(np.float32), meta
+        return img, mask_miss.astype(np.float32), mask_all.astype(np.float32)
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -154,13 +166,22 @@ class Transformer:
         return m[:h - h % s, :w - w % s].reshape(h // s, s, w // s, s).mean(axis=(1, 3))
 
     @staticmethod
-    def _tint(img, rng=None):
-        """HSV-ish tint distortion (reference :98-110) without cv2: random
-        per-channel gain + brightness shift in RGB."""
+    def _tint_params(rng=None):
+        """Draw the tint: three per-channel gains, then the brightness shift."""
         rng = rng or random
+        gains = np.array([1.0 + rng.uniform(-0.15, 0.15) for _ in range(3)], np.float32)
+        shift = rng.uniform(-0.1, 0.1)
+        return gains, shift
+
+    @staticmethod
+    def _apply_tint(img, gains, shift):
         img = img.astype(np.float32)
         if img.max() > 1.5:
             img = img / 255.0
-        gains = np.array([1.0 + rng.uniform(-0.15, 0.15) for _ in range(3)], np.float32)
-        shift = rng.uniform(-0.1, 0.1)
         return np.clip(img * gains + shift, 0.0, 1.0)
+
+    @staticmethod
+    def _tint(img, rng=None):
+        """HSV-ish tint distortion (reference :98-110) without cv2: random
+        per-channel gain + brightness shift in RGB."""
+        return Transformer._apply_tint(img, *Transformer._tint_params(rng))

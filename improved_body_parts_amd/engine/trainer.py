@@ -81,7 +81,7 @@ class Trainer:
     def __init__(self, opt, config, train_dataset, val_dataset=None, *,
                  rank=0, local_rank=0, world_size=1, use_bn=True, sync_bn=None,
                  num_workers=2, checkpoint_dir="checkpoints", log_file=None,
-                 device=None, device_synth_steps=0):
+                 device=None, device_synth_steps=0, device_augment=False):
         self.opt = opt
         self.config = config
         self.rank = rank
@@ -123,6 +123,18 @@ class Trainer:
                 batch_size=opt.batch_size, steps_per_epoch=device_synth_steps,
                 seed=rank + 1, device=self.device,
                 dtype=torch.bfloat16 if self.bf16 else torch.float32)
+        elif (device_augment and self.device.type == "cuda"
+              and hasattr(getattr(train_dataset, "iterator", None), "raw")):
+            # real data, augmentation warp + GT on the device: the host only
+            # reads records, draws the augmentation and packs uint8 sources
+            from ..data import DeviceAugmentLoader
+            self.train_sampler = None
+            self.train_loader = DeviceAugmentLoader(
+                train_dataset, batch_size=opt.batch_size, device=self.device,
+                dtype=torch.bfloat16 if self.bf16 else torch.float32,
+                augment=train_dataset.iterator.augment,
+                shuffle=train_dataset.iterator.shuffle, seed=1,
+                rank=rank, world_size=world_size, drop_last=True)
         else:
             self.train_sampler = (DistributedSampler(train_dataset)
                                   if world_size > 1 else None)

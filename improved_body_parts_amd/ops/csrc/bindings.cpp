@@ -143,6 +143,11 @@ void ensemble_merge(const Tensor& src, const Tensor& chan_main,
                     Tensor& out, double scale, bool accumulate, int64_t cb,
                     int64_t wr, int64_t wc, int64_t span);
 
+// augment.hip
+std::vector<Tensor> augment_warp(const Tensor& packed, const Tensor& desc,
+                                 int64_t H, int64_t W, int64_t stride,
+                                 bool bf16_out);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_v8_geometry", &bn_v8_geometry,
         "debug: [cpb, rpb, rows, grid_y] of the bf16 v8 stats/reduce launch",
@@ -247,4 +252,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ystart"), py::arg("yw"), py::arg("xstart"), py::arg("xw"),
         py::arg("out"), py::arg("scale"), py::arg("accumulate"), py::arg("cb"),
         py::arg("wr"), py::arg("wc"), py::arg("span"));
+  m.def("augment_warp", &augment_warp,
+        "batched affine warp of ragged uint8 records -> [image NHWC, "
+        "mask_miss, mask_all on the stride grid]",
+        py::arg("packed"), py::arg("desc"), py::arg("H"), py::arg("W"),
+        py::arg("stride"), py::arg("bf16_out"));
 }

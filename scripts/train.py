@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--no-sync-bn", action="store_true")
     ap.add_argument("--device-data", type=int, default=0, metavar="STEPS",
                     help="use the on-device GT generator for STEPS batches/epoch")
+    ap.add_argument("--device-augment", action="store_true",
+                    help="COCO h5 data: run the augmentation warp and the GT "
+                         "generator on the GPU instead of in DataLoader workers")
     args = ap.parse_args()
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -83,7 +86,8 @@ def main():
                   local_rank=local_rank, world_size=world_size,
                   sync_bn=not args.no_sync_bn and world_size > 1,
                   num_workers=args.num_workers, checkpoint_dir=args.ckpt_dir,
-                  device_synth_steps=args.device_data)
+                  device_synth_steps=args.device_data,
+                  device_augment=args.device_augment)
     if args.resume:
         trainer.resume(args.resume)
     trainer.fit(args.epochs)
