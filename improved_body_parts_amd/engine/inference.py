@@ -22,7 +22,10 @@ MI355X-first design differences from the reference (behavior preserved):
     pure-Python bottleneck (reference README.md:68). ``matching="device"``
     (``assign_batch``) also moves candidate enumeration, the acceptance
     criteria and the greedy 1-1 matching into one kernel, leaving the host
-    ``find_people`` and one synchronisation per batch.
+    ``find_people`` and one synchronisation per batch. ``assembly="device"``
+    (``people_batch``) adds the greedy person assembly and the COCO keypoint
+    gather as a fourth kernel (people_assemble.hip), bit-identical to
+    ``find_people``: the one copy back then carries finished people only.
   * Everything falls back to the same torch ops on CPU so the pipeline is
     unit-testable without a GPU.
   * Every stage is written once, for a list of images and a planar
@@ -31,6 +34,7 @@ MI355X-first design differences from the reference (behavior preserved):
 """
 from __future__ import annotations
 
+import collections
 import json
 import math
 import os
@@ -41,8 +45,9 @@ import torch.nn.functional as F
 
 from ..config import CanonicalConfig, InferenceParams
 from ..ops._backend import use_hip_for, hip_extension
-from ..ops.assignment import (MAX_PEAKS, OVERFLOW, canonical_peaks,
-                              decode_assignment, limb_match)
+from ..ops.assignment import (MAX_PEAKS, OVERFLOW, assemble_people,
+                              canonical_peaks, decode_assignment, decode_people,
+                              limb_match)
 from ..ops.ensemble import ensemble_merge
 from ..utils import keypoint_heatmap_nms, refine_centroid
 
@@ -489,7 +494,8 @@ def assign_batch(maps, params, config: CanonicalConfig, max_peaks=512,
 # find_people: greedy subset assembly (host — tiny)
 # --------------------------------------------------------------------------
 
-def find_people(connection_all, special_k, all_peaks, params, config: CanonicalConfig):
+def find_people(connection_all, special_k, all_peaks, params, config: CanonicalConfig,
+                stats=None):
     """Greedy person assembly (reference evaluate.py:279-498).
 
     subset rows are (n_slots, 2): slot ``[part] = (candidate_id, confidence)``,
@@ -497,7 +503,9 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
     Semantics preserved from the reference: assign-if-empty (with length
     prior), overwrite-if-better, merge-disjoint-subsets (confidence-gated),
     two-person competition resolution, new-person creation, and final pruning
-    (< 2 parts or mean score < 0.45).
+    (< 2 parts or mean score < 0.45). A dict passed as ``stats`` receives
+    ``max_live``, the most subset rows alive at once (the capacity the device
+    assembly needs), and ``branches``, how often each branch decided.
     """
     len_rate = float(params["len_rate"])
     connection_tole = float(params["connection_tole"])
@@ -505,6 +513,9 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
     n_slots = config.heat_layers + 2  # 18 parts + count + score rows = 20
 
     subset = -1 * np.ones((0, n_slots, 2))
+    count = stats is not None        # bookkeeping only when it is asked for
+    max_live = 0
+    branches = collections.Counter()
     candidate = np.array([p for sub in all_peaks for p in sub], dtype=np.float64) \
         .reshape(-1, 4)
 
@@ -534,17 +545,25 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
                         len_rate * subset[j][-1][1] > length_i:
                     # B slot empty and limb not absurdly longer than what this
                     # person already has: assign
+                    if count:
+                        branches["assign"] += 1
                     subset[j][index_b] = [part_bs[i], score_i]
                     subset[j][-1][0] += 1
                     subset[j][-1][1] = max(length_i, subset[j][-1][1])
                     subset[j][-2][0] += candidate[int(part_bs[i]), 2] + score_i
                 elif int(subset[j][index_b][0]) != int(part_bs[i]):
                     if subset[j][index_b][1] >= score_i:
-                        pass  # existing connection is more confident
+                        # existing connection is more confident
+                        if count:
+                            branches["keep"] += 1
                     else:
                         if len_rate * subset[j][-1][1] <= length_i:
+                            if count:
+                                branches["too_long"] += 1
                             continue
                         # replace: subtract the old point + limb confidence
+                        if count:
+                            branches["overwrite"] += 1
                         subset[j][-2][0] -= candidate[int(subset[j][index_b][0]), 2] \
                             + subset[j][index_b][1]
                         subset[j][index_b] = [part_bs[i], score_i]
@@ -554,6 +573,8 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
                         subset[j][index_b][1] <= score_i:
                     # redundant connection reaching the same keypoint with a
                     # better score: refresh the stored confidence
+                    if count:
+                        branches["refresh"] += 1
                     subset[j][-2][0] -= candidate[int(subset[j][index_b][0]), 2] \
                         + subset[j][index_b][1]
                     subset[j][index_b] = [part_bs[i], score_i]
@@ -571,7 +592,11 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
                     min_tolerance = min(min_limb1, min_limb2)
                     if score_i < connection_tole * min_tolerance or \
                             len_rate * subset[j1][-1][1] <= length_i:
+                        if count:
+                            branches["merge_refused"] += 1
                         continue
+                    if count:
+                        branches["merge"] += 1
                     subset[j1][:-2] += subset[j2][:-2] + 1
                     subset[j1][-2:][:, 0] += subset[j2][-2:][:, 0]
                     subset[j1][-2][0] += score_i
@@ -589,7 +614,11 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
                         continue
                     c1, c2 = int(c1[0][0]), int(c2[0][0])
                     if score_i < subset[j1][c1][1] and score_i < subset[j2][c2][1]:
+                        if count:
+                            branches["compete_skip"] += 1
                         continue
+                    if count:
+                        branches["compete"] += 1
                     small_j, remove_c = (j1, c1)
                     if subset[j1][c1][1] > subset[j2][c2][1]:
                         small_j, remove_c = (j2, c2)
@@ -608,11 +637,17 @@ def find_people(connection_all, special_k, all_peaks, params, config: CanonicalC
                 row[-2][0] = candidate[int(part_as[i]), 2] + \
                     candidate[int(part_bs[i]), 2] + score_i
                 subset = np.concatenate((subset, row[None]), axis=0)
+                if count:
+                    max_live = max(max_live, len(subset))
+                    branches["new"] += 1
 
     # prune: fewer than 2 parts, or mean per-part score below 0.45
     keep = [i for i in range(len(subset))
             if subset[i][-1][0] >= 2 and
             subset[i][-2][0] / subset[i][-1][0] >= 0.45]
+    if count:
+        stats["max_live"] = max_live
+        stats["branches"] = dict(branches)
     return subset[keep], candidate
 
 
@@ -641,35 +676,111 @@ def subsets_to_keypoints(subset, candidate, config: CanonicalConfig):
     return keypoints
 
 
+def _check_modes(matching, assembly):
+    if matching not in ("host", "device"):
+        raise ValueError(f"matching must be 'host' or 'device', got {matching!r}")
+    if assembly not in ("host", "device"):
+        raise ValueError(f"assembly must be 'host' or 'device', got {assembly!r}")
+    if assembly == "device" and matching != "device":
+        raise ValueError("assembly='device' consumes the connection rows of "
+                         "matching='device'")
+
+
+def _people_host(assigned, params, config):
+    """``find_people`` + ``subsets_to_keypoints`` per assigned image."""
+    out = []
+    for all_peaks, connection_all, special_k in assigned:
+        subset, candidate = find_people(connection_all, special_k, all_peaks,
+                                        params, config)
+        out.append(subsets_to_keypoints(subset, candidate, config))
+    return out
+
+
+def people_batch(maps, params, config: CanonicalConfig, max_peaks=512,
+                 max_part=64, max_people=128, assembly="device"):
+    """Peaks, limb matching and person assembly of a planar
+    (N, heat + paf, H, W) pipeline buffer: one list of (coco_keypoints, score)
+    per image. With ``assembly="device"`` on a GPU, ``peaks_batched`` ->
+    ``peaks_canonical`` -> ``limb_match`` -> ``people_assemble`` are queued
+    without a host synchronisation in between, and one copy brings back the
+    people counts, the COCO coordinates and the summed scores of finished
+    people only. An image the kernels flag as overflowed (a part with more than
+    ``max_part`` peaks, or more than ``max_people`` subset rows alive at once)
+    is redone through the host path, so results are never truncated. On CPU
+    maps, or with ``assembly="host"``, this is ``assign_batch`` followed by the
+    host ``find_people``."""
+    if assembly not in ("host", "device"):
+        raise ValueError(f"assembly must be 'host' or 'device', got {assembly!r}")
+    maps = maps.contiguous().float()
+    if assembly == "host" or not use_hip_for(maps):
+        return _people_host(assign_batch(maps, params, config, max_peaks, max_part),
+                            params, config)
+    if max_peaks > MAX_PEAKS:
+        raise ValueError(f"device matching ranks at most {MAX_PEAKS} peaks per "
+                         f"image (max_peaks={max_peaks})")
+    n_parts = config.heat_layers
+    N = maps.shape[0]
+    if N == 0:
+        return []
+    buf = hip_extension().peaks_batched(maps, n_parts, float(params["thre1"]),
+                                        int(params["offset_radius"]), max_peaks)
+    peaks, offsets = canonical_peaks(buf, n_parts)
+    rows, counts = limb_match(maps, peaks, offsets, config.limbs_conn,
+                              config.num_layers - config.paf_layers,
+                              int(params["mid_num"]), float(params["thre2"]),
+                              float(params["connect_ration"]), max_part)
+    n_people, subset, keypoints = assemble_people(
+        peaks, offsets, rows, counts, config.limbs_conn, config.dt_gt_mapping,
+        float(params["len_rate"]), float(params["connection_tole"]),
+        int(params.get("remove_recon", 0)), max_people)
+    # one copy, one synchronisation: int32 and fp64 travel as fp32 bits
+    totals = subset[:, :, n_parts, 0].contiguous()
+    parts = (n_people.view(torch.float32), keypoints, totals.view(torch.float32))
+    flat = torch.cat([t.reshape(-1) for t in parts]).cpu().numpy()
+    host, lo = [], 0
+    for t in parts:
+        host.append(flat[lo:lo + t.numel()].reshape(t.shape))
+        lo += t.numel()
+    out = decode_people(host[0].view(np.int32), host[1],
+                        host[2].view(np.float64), config.dt_gt_mapping)
+    for n in (n for n, people in enumerate(out) if people is None):
+        out[n] = _people_host(_assign_host(maps[n:n + 1], params, config,
+                                           max_peaks), params, config)[0]
+    return out
+
+
 @torch.no_grad()
 def process_batch(images, model, config: CanonicalConfig, params=None,
-                  model_params=None, max_views=16, matching="host"):
+                  model_params=None, max_views=16, matching="host",
+                  assembly="host"):
     """Full pipeline for a list of images (reference evaluate.py:500-542):
     batched forward and ensemble merge, batched peak and limb kernels, then the
     per-image greedy assembly. ``matching="host"`` scores limb candidates on
     the device and matches them on the host; ``"device"`` does both in
-    ``assign_batch``. Returns one list of (coco_keypoints, score) per image, in
+    ``assign_batch``. ``assembly="device"`` (with ``matching="device"``) also
+    assembles the people on the device (``people_batch``), so only finished
+    people come back. Returns one list of (coco_keypoints, score) per image, in
     input order."""
-    if matching not in ("host", "device"):
-        raise ValueError(f"matching must be 'host' or 'device', got {matching!r}")
+    _check_modes(matching, assembly)
     params, model_params = _resolve_params(params, model_params)
     results = [None] * len(images)
     for idxs, maps in _predict_groups(images, model, config, params,
                                       model_params, max_views):
-        assign = assign_batch if matching == "device" else _assign_host
-        assigned = assign(maps, params, config)
-        for i, (all_peaks, connection_all, special_k) in zip(idxs, assigned):
-            subset, candidate = find_people(connection_all, special_k, all_peaks,
-                                            params, config)
-            results[i] = subsets_to_keypoints(subset, candidate, config)
+        if assembly == "device":
+            people = people_batch(maps, params, config)
+        else:
+            assign = assign_batch if matching == "device" else _assign_host
+            people = _people_host(assign(maps, params, config), params, config)
+        for i, found in zip(idxs, people):
+            results[i] = found
     return results
 
 
 def process(image, model, config: CanonicalConfig, params=None, model_params=None,
-            matching="host"):
+            matching="host", assembly="host"):
     """``process_batch`` for one image -> list of (coco_keypoints, score)."""
     return process_batch([image], model, config, params, model_params,
-                         matching=matching)[0]
+                         matching=matching, assembly=assembly)[0]
 
 
 def format_results(keypoints, res_file):

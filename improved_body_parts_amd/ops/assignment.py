@@ -12,8 +12,12 @@ two ops here keep all of that on the device (``csrc/limb_match.hip``):
     segments of every (image, limb type) and returns finished connection rows.
 
 ``decode_assignment`` turns host copies of their outputs into the structures
-``find_people`` consumes. On CPU tensors both ops run the existing host
-functions, which are also the oracle the kernels are tested against.
+``find_people`` consumes. ``assemble_people`` (``csrc/people_assemble.hip``)
+goes one stage further and runs ``find_people`` and ``subsets_to_keypoints`` on
+those device outputs, bit-identically; ``decode_people`` turns host copies of
+its outputs into the result format of ``process_batch``. On CPU tensors all
+three ops run the existing host functions, which are also the oracle the
+kernels are tested against.
 """
 from __future__ import annotations
 
@@ -28,6 +32,9 @@ MAX_PART = 64        # kMatchMaxPart in limb_match.hip: one 64-bit mask per side
 MAX_PEAKS = 512      # kCanonMaxPeaks: rows peaks_canonical stages in LDS
 OVERFLOW = -2        # count of a limb whose part has more than max_part peaks
 NO_PEAKS = -1        # count of a limb with a part that has no peak (special_k)
+MAX_PEOPLE = 128     # kAsmMaxPeople in people_assemble.hip: subset rows in LDS
+N_PARTS = 18         # kAsmParts: part slots of a subset row
+N_KEYPOINTS = 17     # kAsmKeypoints: COCO keypoints per person
 
 
 def _buffer_counts(buf_np, max_peaks):
@@ -176,4 +183,159 @@ def decode_assignment(peaks, offsets, rows, counts):
                 cnt = min(cnt, rows.shape[2])
                 connection_all.append(rows[n, k, :cnt].astype(np.float64))
         out.append((all_peaks, connection_all, special_k))
+    return out
+
+
+# --------------------------------------------------------------------------
+# person assembly (csrc/people_assemble.hip)
+# --------------------------------------------------------------------------
+
+def _mapping_table(dt_gt_mapping, n_parts):
+    """``{part: COCO slot or None}`` (or a sequence) -> a tuple of ``n_parts``
+    ints, -1 for a part without a COCO slot."""
+    if isinstance(dt_gt_mapping, dict):
+        # the last key mapped to a slot wins on the host; so does the highest
+        # part index in the kernel
+        if list(dt_gt_mapping) != sorted(dt_gt_mapping):
+            raise ValueError("dt_gt_mapping keys must ascend")
+        seq = [dt_gt_mapping.get(p) for p in range(n_parts)]
+        if set(dt_gt_mapping) - set(range(n_parts)):
+            raise ValueError("dt_gt_mapping names parts outside [0, n_parts)")
+    else:
+        seq = list(dt_gt_mapping)
+    table = tuple(-1 if g is None else int(g) for g in seq)
+    if len(table) != n_parts or any(not -1 <= g < N_KEYPOINTS for g in table):
+        raise ValueError(f"dt_gt_mapping must give {n_parts} slots in "
+                         f"[0, {N_KEYPOINTS}) or None")
+    return table
+
+
+@functools.lru_cache(maxsize=16)
+def _device_mapping(device, table):
+    return torch.tensor(table, dtype=torch.int32, device=device)
+
+
+def assemble_people(peaks, offsets, rows, counts, limbs, dt_gt_mapping, len_rate,
+                    connection_tole, remove_recon, max_people=MAX_PEOPLE):
+    """Greedy person assembly (``find_people``) and ``subsets_to_keypoints`` of
+    every image, on the device outputs of :func:`canonical_peaks` and
+    :func:`limb_match`.
+
+    ``limbs``: (partA, partB) per limb type; ``dt_gt_mapping``: COCO slot (or
+    ``None``) per part, a dict or a sequence. Returns
+    ``(n_people, subset, keypoints)``: int32 (N,), fp64
+    (N, max_people, n_parts + 2, 2) subset rows in the layout and order of
+    ``find_people``, and fp32 (N, max_people, 17, 2) COCO coordinates with
+    ``(0, 0)`` for a missing keypoint. Only rows ``[0, n_people[n])`` of an
+    image are defined. ``n_people[n] == OVERFLOW`` marks an image with an
+    overflowed limb, a peak id outside the image's peaks, or more than
+    ``max_people`` subset rows alive at once; the caller redoes it on the host.
+    """
+    limbs = tuple((int(a), int(b)) for a, b in limbs)
+    max_people = int(max_people)
+    if not 1 <= max_people <= MAX_PEOPLE:
+        raise ValueError(f"max_people must be in [1, {MAX_PEOPLE}]")
+    if peaks.dim() != 3 or peaks.shape[2] != 5 or peaks.shape[1] < 1 or \
+            peaks.dtype != torch.float32:
+        raise ValueError("peaks must be fp32 (N, max_peaks, 5)")
+    N = peaks.shape[0]
+    if offsets.dim() != 2 or offsets.shape[0] != N or \
+            offsets.shape[1] != N_PARTS + 1 or offsets.dtype != torch.int32:
+        raise ValueError(f"offsets must be int32 (N, {N_PARTS + 1})")
+    if rows.dim() != 4 or rows.shape[0] != N or rows.shape[1] != len(limbs) or \
+            not 1 <= rows.shape[2] <= MAX_PART or rows.shape[3] != 6 or \
+            rows.dtype != torch.float32:
+        raise ValueError(f"rows must be fp32 (N, L, max_part <= {MAX_PART}, 6)")
+    if counts.shape != rows.shape[:2] or counts.dtype != torch.int32:
+        raise ValueError("counts must be int32 (N, L)")
+    if not limbs or any(not (0 <= a < N_PARTS and 0 <= b < N_PARTS)
+                        for a, b in limbs):
+        raise ValueError("limbs must name parts in [0, n_parts)")
+    table = _mapping_table(dt_gt_mapping, N_PARTS)
+    if use_hip_for(peaks):
+        if peaks.shape[1] > MAX_PEAKS:
+            raise ValueError(f"device assembly stages at most {MAX_PEAKS} peaks "
+                             f"per image (max_peaks={peaks.shape[1]})")
+        n_people, subset, keypoints = hip_extension().people_assemble(
+            peaks.contiguous(), offsets.contiguous(), rows.contiguous(),
+            counts.contiguous(), _device_limbs(peaks.device, limbs),
+            _device_mapping(peaks.device, table), float(len_rate),
+            float(connection_tole), int(remove_recon), max_people)
+        return n_people, subset, keypoints
+    return _assemble_host(peaks, offsets, rows, counts, limbs, table,
+                          float(len_rate), float(connection_tole),
+                          int(remove_recon), max_people)
+
+
+def _assemble_host(peaks, offsets, rows, counts, limbs, table, len_rate,
+                   connection_tole, remove_recon, max_people):
+    """CPU fallback of ``assemble_people``: ``decode_assignment``, the host
+    ``find_people`` and ``subsets_to_keypoints``, written into the op's
+    layout."""
+    from types import SimpleNamespace
+    from ..engine.inference import find_people, subsets_to_keypoints
+
+    config = SimpleNamespace(
+        limbs_conn=list(limbs), heat_layers=N_PARTS,
+        dt_gt_mapping={p: (None if g < 0 else g) for p, g in enumerate(table)})
+    params = {"len_rate": len_rate, "connection_tole": connection_tole,
+              "remove_recon": remove_recon}
+    N = peaks.shape[0]
+    n_people = np.zeros(N, dtype=np.int32)
+    subset = np.zeros((N, max_people, N_PARTS + 2, 2), dtype=np.float64)
+    keypoints = np.zeros((N, max_people, N_KEYPOINTS, 2), dtype=np.float32)
+    decoded = decode_assignment(peaks.numpy(), offsets.numpy(), rows.numpy(),
+                                counts.numpy())
+    for n, (all_peaks, connection_all, special_k) in enumerate(decoded):
+        n_cand = sum(len(sub) for sub in all_peaks)
+        if any(c is None for c in connection_all) or any(
+                len(c) and not ((c[:, :2] >= 0) & (c[:, :2] < n_cand)).all()
+                for c in connection_all):
+            n_people[n] = OVERFLOW
+            continue
+        stats = {}
+        sub, candidate = find_people(connection_all, special_k, all_peaks,
+                                     params, config, stats=stats)
+        if stats["max_live"] > max_people:
+            n_people[n] = OVERFLOW
+            continue
+        n_people[n] = len(sub)
+        subset[n, :len(sub)] = sub
+        for i, (coco, _) in enumerate(subsets_to_keypoints(sub, candidate, config)):
+            keypoints[n, i] = [(0.0, 0.0) if pt is None else pt for pt in coco]
+    return (torch.from_numpy(n_people), torch.from_numpy(subset),
+            torch.from_numpy(keypoints))
+
+
+def decode_people(n_people, keypoints, totals, dt_gt_mapping):
+    """Host copies of :func:`assemble_people` outputs (numpy arrays) -> one
+    list of ``(coco_keypoints, score)`` per image, the result format of
+    ``process_batch``. ``totals``: fp64 (N, max_people), column 0 of subset row
+    ``n_parts`` (the summed score). ``coco_keypoints`` holds 17 ``(x, y)``
+    tuples, ``None`` for a COCO slot no part maps to; the score is
+    ``1 - 1 / total``. An image flagged ``OVERFLOW`` gives ``None``."""
+    n_people = np.asarray(n_people)
+    totals = np.asarray(totals, dtype=np.float64)
+    table = _mapping_table(dt_gt_mapping, N_PARTS)
+    unmapped = [g for g in range(N_KEYPOINTS) if g not in table]
+    # only rows below an image's count are defined: gather those, image by
+    # image in order, and leave the rest of the buffers alone
+    valid = np.arange(totals.shape[1])[None, :] < n_people[:, None]
+    totals = totals[valid]
+    with np.errstate(divide="ignore"):
+        scores = np.where(totals > 0, 1 - 1.0 / totals, 0.0).tolist()
+    points = np.asarray(keypoints)[valid].astype(np.float64).tolist()
+    out, lo = [], 0
+    for cnt in n_people.tolist():
+        if cnt < 0:
+            out.append(None)
+            continue
+        people = []
+        for i in range(lo, lo + cnt):
+            coco = [tuple(pt) for pt in points[i]]
+            for g in unmapped:
+                coco[g] = None
+            people.append((coco, scores[i]))
+        out.append(people)
+        lo += cnt
     return out

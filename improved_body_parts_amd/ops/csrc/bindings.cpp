@@ -136,6 +136,13 @@ std::vector<Tensor> limb_match(const Tensor& maps, const Tensor& peaks,
                                double thre2, double connect_ration,
                                int64_t max_part);
 
+// people_assemble.hip
+std::vector<Tensor> people_assemble(const Tensor& peaks, const Tensor& offsets,
+                                    const Tensor& rows, const Tensor& counts,
+                                    const Tensor& limbs, const Tensor& dt_gt,
+                                    double len_rate, double connection_tole,
+                                    int64_t remove_recon, int64_t max_people);
+
 // ensemble_merge.hip
 void ensemble_merge(const Tensor& src, const Tensor& chan_main,
                     const Tensor& chan_flip, const Tensor& ystart,
@@ -242,6 +249,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("maps"), py::arg("peaks"), py::arg("offsets"), py::arg("limbs"),
         py::arg("first_limb_plane"), py::arg("mid_num"), py::arg("thre2"),
         py::arg("connect_ration"), py::arg("max_part"));
+  m.def("people_assemble", &people_assemble,
+        "per image: greedy person assembly over limb_match rows + COCO keypoints",
+        py::arg("peaks"), py::arg("offsets"), py::arg("rows"), py::arg("counts"),
+        py::arg("limbs"), py::arg("dt_gt"), py::arg("len_rate"),
+        py::arg("connection_tole"), py::arg("remove_recon"),
+        py::arg("max_people"));
   m.def("peaks_batched", &peaks_batched,
         "fused NMS + centroid refinement over a planar batch, per-image counters",
         py::arg("maps"), py::arg("heat_layers"), py::arg("thre"),

@@ -32,7 +32,7 @@ except Exception:  # pragma: no cover
 
 from .config import GetConfig, TrainingOpt
 from .config.inference_params import InferenceParams
-from .engine.inference import process, process_batch
+from .engine.inference import _check_modes, process, process_batch
 from .models import NetworkEval
 
 
@@ -41,11 +41,11 @@ class PoseService:
 
     def __init__(self, config_name: str = "Canonical", nstack: int = 4,
                  checkpoint: Optional[str] = None, device: Optional[str] = None,
-                 bf16: Optional[bool] = None, matching: str = "host"):
-        if matching not in ("host", "device"):
-            raise ValueError(
-                f"matching must be 'host' or 'device', got {matching!r}")
+                 bf16: Optional[bool] = None, matching: str = "host",
+                 assembly: str = "host"):
+        _check_modes(matching, assembly)
         self.matching = matching
+        self.assembly = assembly
         self.config = GetConfig(config_name)
         self.opt = TrainingOpt(nstack=nstack, batch_size=1)
         self.device = torch.device(device or
@@ -73,7 +73,8 @@ class PoseService:
         """image (H, W, 3) float32 in [0,1] -> list of people dicts."""
         with self._lock, torch.no_grad():
             people = process(image, self.model, self.config, self.params,
-                             self.model_params, matching=self.matching)
+                             self.model_params, matching=self.matching,
+                             assembly=self.assembly)
         return self._people_dicts(people)
 
     def infer_many(self, images):
@@ -82,7 +83,8 @@ class PoseService:
         with self._lock, torch.no_grad():
             batch = process_batch(list(images), self.model, self.config,
                                   self.params, self.model_params,
-                                  matching=self.matching)
+                                  matching=self.matching,
+                                  assembly=self.assembly)
         return [self._people_dicts(people) for people in batch]
 
     @staticmethod

@@ -23,6 +23,10 @@ ap.add_argument("--matching", choices=["host", "device"], nargs="+",
                 default=["host"],
                 help="where limb candidates are matched; several values "
                      "alternate inside each repeat on the same model")
+ap.add_argument("--assembly", choices=["host", "device"], nargs="+",
+                default=["host"],
+                help="where people are assembled ('device' only pairs with "
+                     "--matching device); several values alternate as well")
 args = ap.parse_args()
 
 config = GetConfig("Canonical")
@@ -69,19 +73,21 @@ ds = SyntheticPoseDataset(config, length=64, render=True, seed=3)
 imgs = [ds.generate(i % 64)[0] for i in range(args.images)]
 
 
-def measure(batch_size, matching):
+def measure(batch_size, matching, assembly):
     """Warm up, then time one pass over ``imgs``; returns (img/s, people)."""
     if batch_size > 1:
         def run(batch):
             return sum(len(r) for r in process_batch(batch, model, config, p, mp,
-                                                     matching=matching))
+                                                     matching=matching,
+                                                     assembly=assembly))
         chunks = [imgs[i:i + batch_size] for i in range(0, len(imgs), batch_size)]
         # warm every batch size the timed loop uses
         for n in sorted({len(c) for c in chunks}):
             run(imgs[:n])
     else:
         def run(batch):
-            return len(process(batch[0], model, config, p, mp, matching=matching))
+            return len(process(batch[0], model, config, p, mp, matching=matching,
+                               assembly=assembly))
         chunks = [[img] for img in imgs]
         for img in imgs[:4]:
             run([img])                               # warmup
@@ -96,11 +102,15 @@ def measure(batch_size, matching):
 # several --batch values alternate inside each repeat, so they see the same
 # machine state and their spread can be compared
 for rep in range(args.repeats):
-    for b, matching in ((b, m) for b in args.batch for m in args.matching):
-        fps, n_people = measure(b, matching)
+    for b, matching, assembly in ((b, m, a) for b in args.batch
+                                  for m in args.matching for a in args.assembly
+                                  if a == "host" or m == "device"):
+        fps, n_people = measure(b, matching, assembly)
         label = f"process_batch(batch={b})" if b > 1 else "process()"
         if matching != "host":
             label = label[:-1] + (", " if b > 1 else "") + f"matching={matching})"
+        if assembly != "host":
+            label = label[:-1] + f", assembly={assembly})"
         print(f"end-to-end {label} {fps:.1f} img/s over {len(imgs)} images "
               f"({n_people} people found; 512^2, {opt.nstack}-stack, single scale, "
               f"flip ensemble, {'trained ' + str(args.train_steps) + ' steps' if args.train_steps else 'random-init'})",

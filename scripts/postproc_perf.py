@@ -11,11 +11,15 @@ realistic multi-person maps at the reference's full-image resolution.
     python scripts/postproc_perf.py --cpu      # host-only reference path
     python scripts/postproc_perf.py --matching device --batch 8
                                                # matching on the device too
+    python scripts/postproc_perf.py --matching device --assembly device --batch 8
+                                               # and the person assembly
 
 ``--matching device`` runs ``assign_batch`` (peaks_canonical + limb_match, one
 synchronisation per call); it launches one workgroup per (image, limb type), so
 only ``--batch N`` images per call fill the GPU. ``--matching host --batch N``
-runs the batched host path on the same planar buffers.
+runs the batched host path on the same planar buffers. ``--assembly device``
+(with ``--matching device``) runs ``people_batch``: the greedy person assembly
+is a fourth kernel and only finished people are copied back.
 """
 from __future__ import annotations
 
@@ -33,7 +37,7 @@ from improved_body_parts_amd.config import GetConfig, InferenceParams  # noqa: E
 from improved_body_parts_amd.data import Heatmapper, sample_people  # noqa: E402
 from improved_body_parts_amd.engine.inference import (  # noqa: E402
     assign_batch, find_connections, find_connections_batch, find_peaks,
-    find_peaks_batch, find_people, subsets_to_keypoints)
+    find_peaks_batch, find_people, people_batch, subsets_to_keypoints)
 
 
 def main():
@@ -43,10 +47,13 @@ def main():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--people", type=int, default=6)
     ap.add_argument("--matching", choices=["host", "device"], default="host")
+    ap.add_argument("--assembly", choices=["host", "device"], default="host")
     ap.add_argument("--batch", type=int, default=1, help="images per call")
     args = ap.parse_args()
     if args.batch < 1:
         ap.error("--batch must be >= 1")
+    if args.assembly == "device" and args.matching != "device":
+        ap.error("--assembly device needs --matching device")
 
     config = GetConfig("Canonical")
     params, _ = InferenceParams().as_params_dict()
@@ -112,6 +119,9 @@ def batched(args, scenes, params, config, device):
         return [(pk, c, sk) for pk, (c, sk) in zip(peaks, conns)]
 
     def run(maps):
+        if args.assembly == "device":
+            return sum(len(people) for people in
+                       people_batch(maps, params, config))
         found = 0
         for all_peaks, conn, special in assign(maps):
             subset, cand = find_people(conn, special, all_peaks, params, config)
@@ -129,7 +139,9 @@ def batched(args, scenes, params, config, device):
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     fps = args.images / dt
-    print(f"device={device} matching={args.matching} batch={args.batch} "
+    mode = args.matching if args.assembly == "host" else \
+        f"{args.matching} assembly={args.assembly}"
+    print(f"device={device} matching={mode} batch={args.batch} "
           f"images={args.images} size={H} "
           f"people_found={found} assignment_fps={fps:.1f} "
           f"({dt / args.images * 1e3:.1f} ms/img) "

@@ -17,12 +17,20 @@ def main():
     ap.add_argument("--nstack", type=int, default=4)
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
+    ap.add_argument("--matching", choices=["host", "device"], default="host",
+                    help="where limb candidates are matched")
+    ap.add_argument("--assembly", choices=["host", "device"], default="host",
+                    help="where people are assembled; 'device' needs "
+                         "--matching device")
     args = ap.parse_args()
+    if args.assembly == "device" and args.matching != "device":
+        ap.error("--assembly device needs --matching device")
 
     from improved_body_parts_amd.serve import create_app
     import uvicorn
     app = create_app(config_name=args.config, nstack=args.nstack,
-                     checkpoint=args.checkpoint)
+                     checkpoint=args.checkpoint, matching=args.matching,
+                     assembly=args.assembly)
     uvicorn.run(app, host=args.host, port=args.port)
 
 
